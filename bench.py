@@ -26,6 +26,11 @@ Scaling (--scaling, default strong): config C as BASELINE.json states it —
 100k/N rows, decode of its 100k/N pods). --scaling weak: every GPU brings its
 own 100k-pod batch (N x 100k pods per step), a labelled extra.
 
+A plain run sets up, brings the GPU clock up (timed_steady), warms up, times the
+K steps, writes --dump-outputs and prints the headline line. Everything below
+runs only with --full, after the timed region: the oracle parity check of the
+last timed batch (exit 5 on a mismatch), and the extra fields.
+
 Extra fields (rank 0): pods/s per SURVEY §8(d) — ms_schedule_batch_compact on
 host arrays (8 B pods in, the cycle, bind commit, 8 B results out; single
 shard: one launch over pinned host memory; 1 warm-up, median of 5; with N > 1
@@ -34,8 +39,13 @@ the collective host call over the communicator; `e2e`: ms_schedule_batch with
 `device_pods_per_s`, the VALU-issue roofline of the timed kernel with its HBM
 figures, and the CPU baseline (oracle, OpenMP, on the box's host cores).
 
-Launch: python bench.py [--gpus 1 --steps K --warmup W]; for N > 1 the driver
-uses torch.distributed.run with one rank per GPU.
+Launch: python bench.py [--gpus 1 --steps K --warmup W] [--full] [--dump-outputs DIR];
+for N > 1 the driver uses torch.distributed.run with one rank per GPU.
+
+--dump-outputs DIR: the decoded results of the last timed step (node, code,
+score, plugin_mask per pod: what the caller of the timed path receives) as
+DIR/<field>.npy, float64. Inputs are synthetic and seeded (--seed), so two
+builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -87,10 +97,19 @@ def parse():
                     help="strong (default): the config's P pods split over the GPUs (BASELINE config C); weak: "
                          "every GPU brings the config's pod batch, so the job schedules N x P pods")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline sample length")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the e2e measurements and configs B, D, E")
-    ap.add_argument("--no-configs", action="store_true", help="skip configs B, D, E (device + CPU baselines)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the oracle parity check of the last timed batch, the e2e host calls, "
+                         "the roofline, the CPU baseline and configs B, C_names, D, E, TT, NAM (a plain run sets up, "
+                         "warms up, times the steps and prints the headline line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's results (what the caller of the timed path "
+                         "receives: node, code, score, plugin_mask per pod) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: target CPU-baseline sample length")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the e2e measurements and configs B, D, E")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="--full without configs B, D, E (device + CPU baselines)")
     ap.add_argument("--profile-json", default=os.path.join(ROOT, "profiles", "r06o_pmc_C.json"),
                     help="rocprofv3 counter summary of the timed kernel (tools/profile_pp.sh)")
     ap.add_argument("--profile-shard-prefix", default=os.path.join(ROOT, "profiles", "r04zh_pmc_shard"),
@@ -584,6 +603,28 @@ def slice_parity(n_nodes, seed, pods_np, a, b, res, threads, prefix=1024):
     return {"ok": bool(ok), "n": k}
 
 
+DUMP_FIELDS = ("node", "code", "score", "plugin_mask")
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # all ranks' files together
+
+
+def dump_outputs(path, res, first, rank, world):
+    """--dump-outputs: this rank's decoded results of the last timed step (pods
+    [first, first + len(res)) of the batch) as <path>/<field>.npy, float64 (every
+    field is an integer below 2^53, so the conversion is exact). With N > 1 each
+    rank writes <field>_rank<r>.npy. Beyond the size budget a fixed, seeded sample
+    of the pods is written, with their batch indices as pod_index."""
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    cap = DUMP_MAX_BYTES // max(1, world) // (8 * (len(DUMP_FIELDS) + 1))
+    idx = None
+    if len(res) > cap:
+        idx = np.sort(np.random.default_rng(20240229).choice(len(res), size=cap, replace=False))
+        res = res[idx]
+        np.save(os.path.join(path, f"pod_index{suffix}.npy"), (idx + first).astype(np.float64))
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(path, f"{f}{suffix}.npy"), np.ascontiguousarray(res[f]).astype(np.float64))
+
+
 RANK_FIELDS = ("rank", "comm_rank", "comm_world", "wall_s", "device_ms_per_step", "kernel_ms", "parity_ok",
                "parity_pods", "slice_first", "slice_end", "pods_scheduled")
 
@@ -722,13 +763,17 @@ def main():
         t = torch.tensor([ok], dtype=torch.int64, device=dev)
         dist.all_reduce(t)
         ok = int(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, cyc.a, rank, world)
 
-    # self-verification (after the timed region): the rank's communicator, its own
-    # step times and the parity of its decoded slice; gathered to rank 0
-    from minisched_amd.hostinfo import cpu_threads
-
+    # the rank's communicator and its own step times, gathered to rank 0; --full:
+    # self-verification (after the timed region), the parity of its decoded slice
     inf = eng.info()
-    chk = slice_parity(N, args.seed, pods_np, cyc.a, cyc.b, res, max(1, cpu_threads() // max(1, world)))
+    chk = {"ok": True, "n": 0}
+    if args.full:
+        from minisched_amd.hostinfo import cpu_threads
+
+        chk = slice_parity(N, args.seed, pods_np, cyc.a, cyc.b, res, max(1, cpu_threads() // max(1, world)))
     coll_dev = dev if backend == "nccl" else torch.device("cpu")
     rows = gather_rows([rank, inf.comm_rank, inf.comm_world if use_lib else -1, elapsed_rank, step_dev_ms, kernel_ms,
                         1.0 if chk["ok"] else 0.0, chk["n"], cyc.a, cyc.b,
@@ -736,12 +781,12 @@ def main():
     per_rank = [{k: (int(v) if k not in ("wall_s", "device_ms_per_step", "kernel_ms") else v)
                  for k, v in zip(RANK_FIELDS, r)} for r in rows]
     for r in per_rank:
-        r["parity_ok"] = bool(r["parity_ok"])
+        r["parity_ok"] = bool(r["parity_ok"]) if args.full else None
         r["ms_per_step"] = r.pop("wall_s") * 1e3 / args.steps
-    parity_all = all(r["parity_ok"] for r in per_rank)
+    parity_all = all(r["parity_ok"] for r in per_rank) if args.full else True
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # SURVEY §8(d) pods/s: ms_schedule_batch on host arrays (collective with N > 1)
         for key, compact in (("e2e_compact", True), ("e2e", False)):
             try:
@@ -756,7 +801,7 @@ def main():
         kernel_s = kernel_ms * 1e-3
         # N > 1: this rank's shard sweep, counters of the same shard shape (tools/profile_shards.sh)
         prof_path = args.profile_json if world == 1 else f"{args.profile_shard_prefix}{hi - lo}.json"
-        pj = load_profile(prof_path, hi - lo, P)
+        pj = load_profile(prof_path, hi - lo, P) if args.full else None
         valu = pj.get("SQ_INSTS_VALU") if pj else None
         traffic = pj.get("hbm_bytes_per_launch") if pj else None
         roofline = {
@@ -824,7 +869,10 @@ def main():
             "device_pods_per_s": P * args.steps / elapsed,
             "device_ms_per_step": step_dev_ms,
             "pods_scheduled": ok,
-            "roofline": roofline,
+            "full": bool(args.full),
+            # the dominant kernel alone (timed_steady, the clock ramp before the warm-up steps)
+            "kernel_ms": kernel_ms,
+            "roofline": roofline if args.full else None,
             "cpu_baseline": None,
             # each rank's communicator (RCCL rank / world as the
             # library reports them; -1 without the in-library communicator), its own
@@ -834,16 +882,17 @@ def main():
             "verify": {
                 "backend": backend if world > 1 else None,
                 "in_library_rccl": bool(cyc.library),
-                "parity_ok_all_ranks": parity_all,
-                "parity_check": "oracle msor_schedule_nunn_omp over all nodes, first <= 1024 pods of each rank's "
-                                "decoded slice of the last timed batch (node, code, score, plugin mask)",
+                "parity_ok_all_ranks": parity_all if args.full else None,
+                "parity_check": ("oracle msor_schedule_nunn_omp over all nodes, first <= 1024 pods of each rank's "
+                                 "decoded slice of the last timed batch (node, code, score, plugin mask)"
+                                 if args.full else "not run (--full)"),
                 "per_rank": per_rank,
             },
         }
         line.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, args.seed, args.cpu_seconds)
-        if world == 1 and not args.no_extras and not args.no_configs:
+        if args.full and world == 1 and not args.no_extras and not args.no_configs:
             try:
                 line["configs"] = other_configs(args, dev, stream)
                 cn = line["configs"].get("C_names")
