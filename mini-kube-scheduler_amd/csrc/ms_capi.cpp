@@ -55,13 +55,12 @@ void free_all(ms_ctx *c) {
         c->t.allowed_pods = c->t.pod_count = nullptr;
         c->t.alloc_cpu = c->t.alloc_mem = c->t.req_cpu = c->t.req_mem = c->t.nz_cpu = c->t.nz_mem = nullptr;
     }
-    void *dev[] = {c->t.planes, c->t.zone, c->t.label2, c->d_terms, c->d_nam, c->t.flags, c->t.digit, c->t.allowed_pods, c->t.pod_count, c->t.alloc_cpu,
-                   c->t.alloc_mem, c->t.req_cpu, c->t.req_mem, c->t.nz_cpu, c->t.nz_mem,
+    void *dev[] = {c->t.planes, c->d_terms, c->d_nam,
                    c->d_pods, c->d_res, c->d_keys, c->d_flags, c->d_deltas, c->d_one,
                    c->d_tile_keys, c->d_tile_flags, c->d_spec, c->d_spec_flags, c->d_top4, c->d_top4_rec, c->d_prev, c->d_prev_rec, c->d_overflow,
                    c->d_podc, c->d_resc,
-                   c->d_merged, c->d_merged_flags, c->d_drow, c->d_top_ext, c->t.taints, c->d_tt,
-                   c->d_merge_tags, c->d_merge_ctr};
+                   c->d_merged, c->d_merged_flags, c->d_drow, c->d_top_ext, c->d_tt,
+                   c->d_merge_tags};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     if (c->h_podz) (void)hipHostFree(c->h_podz);
@@ -178,16 +177,13 @@ int chain_back(ms_ctx *c, hipStream_t s, bool recorded) {
     return MS_OK;
 }
 
-// The in-step merge's counter (a counter, or one slot per sweep workgroup: at most 255).
-hipError_t ctr_alloc(uint32_t **p) { return hipMalloc((void **)p, 1024); }
-
 // Sequential-engine scratch for n_tiles tiles, kSeqBufs batches deep (the
 // single-stream steps use two sets; the node-sharded candidates up to three).
 int ensure_tiles(ms_ctx *c, uint32_t n_tiles) {
     if (n_tiles <= c->tile_cap) return MS_OK;
     MS_HIP(c, hipDeviceSynchronize());  // no batch still reads the old buffers
     void *old[] = {c->d_tile_keys, c->d_tile_flags, c->d_spec, c->d_spec_flags, c->d_top4, c->d_top4_rec, c->d_prev,
-                   c->d_prev_rec, c->d_drow, c->d_top_ext, c->d_merge_tags, c->d_merge_ctr};
+                   c->d_prev_rec, c->d_drow, c->d_top_ext, c->d_merge_tags};
     for (void *q : old)
         if (q) (void)hipFree(q);
     c->d_tile_keys = nullptr;
@@ -201,7 +197,6 @@ int ensure_tiles(ms_ctx *c, uint32_t n_tiles) {
     c->d_drow = nullptr;
     c->d_top_ext = nullptr;
     c->d_merge_tags = nullptr;
-    c->d_merge_ctr = nullptr;
     c->tile_cap = 0;
     // (ms_seq_candidates_device uses the same buffers for up to kSeqBufs * B pods)
     const size_t B = seq_batch_limit(), NB = kSeqBufs * B, n = NB * n_tiles;
@@ -215,8 +210,7 @@ int ensure_tiles(ms_ctx *c, uint32_t n_tiles) {
         hipMalloc((void **)&c->d_prev_rec, 2 * seq_prev_cap() * seq_rec_fields() * sizeof(int64_t)) != hipSuccess ||
         hipMalloc((void **)&c->d_drow, (size_t)n_tiles * kFullWaveTile * sizeof(DRow)) != hipSuccess ||
         hipMalloc((void **)&c->d_top_ext, NB * seq_topk() * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&c->d_merge_tags, NB * sizeof(uint32_t)) != hipSuccess ||
-        ctr_alloc(&c->d_merge_ctr) != hipSuccess)
+        hipMalloc((void **)&c->d_merge_tags, NB * sizeof(uint32_t)) != hipSuccess)
         return fail(c, MS_E_OOM, "sequential-engine scratch");
     MS_HIP(c, hipMemsetAsync(c->d_merge_tags, 0, NB * sizeof(uint32_t), c->stream));
     MS_HIP(c, hipMemsetAsync(c->d_spec, 0, NB * sizeof(unsigned long long), c->stream));
@@ -259,9 +253,6 @@ int run_sequential(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resu
         const uint32_t room = (uint32_t)std::max(2, c->num_cus) - 1u;
         const uint32_t tr = (cdiv(rows, room) + 15u) / 16u * 16u;
         tq.tile_rows = std::min<uint32_t>((uint32_t)kFullWaveTile, std::max<uint32_t>(64u, tr));
-#ifdef MS_TILE_ROWS  // (A/B builds: a fixed tile height)
-        tq.tile_rows = MS_TILE_ROWS;
-#endif
     }
     const uint32_t n_tiles = cdiv(rows, tq.tile_rows);
     int rc = ensure_tiles(c, n_tiles);
@@ -292,10 +283,7 @@ int run_sequential(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resu
         // 4096:32 / 8192:32 / 16384:32 / 16384:64 / 32768:64 measured slower,
         // r05k_e_warm.txt). Round 6, with the validator's ranks 4..7 walk: none /
         // 4,096 / 8,192 pods 32.3 / 31.1 / 31.2 ms (profiles/r06j_e_warm_ab.txt).
-#ifndef MS_WARM_PODS
-#define MS_WARM_PODS 4096
-#endif
-        constexpr uint32_t kWarmPods = MS_WARM_PODS, kWarmBatch = 64;
+        constexpr uint32_t kWarmPods = 4096, kWarmBatch = 64;
         auto batch_at = [&](uint32_t s0) { return s0 < kWarmPods ? std::min(kWarmBatch, B) : B; };
         const uint32_t nb0 = std::min(batch_at(0), n_pods);
         const char *merge_env = getenv("MINISCHED_SEQ_MERGE");
@@ -308,7 +296,6 @@ int run_sequential(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resu
             // previous run whose 2-bit tag happened to match was taken as swept
             // (config E's second 65,536-pod chunk, pods 64..127 of its first
             // full-size batch: tests/test_gpu_fullsize.py, profiles/r05n_e_probe.txt).
-            MS_HIP(c, hipMemsetAsync(c->d_merge_ctr, 0, 1024, s));
             MS_HIP(c, hipMemsetAsync(c->d_tile_keys, 0,
                                      (size_t)kSeqBufs * cells_per_set * seq_topk() * sizeof(unsigned long long), s));
             MS_HIP(c, hipMemsetAsync(c->d_tile_flags, 0, (size_t)kSeqBufs * cells_per_set * sizeof(uint32_t), s));
@@ -317,25 +304,55 @@ int run_sequential(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resu
         MS_HIP(c, launch_topk_merge(c->d_tile_keys, c->d_tile_flags, nb0, n_tiles, c->d_top4, c->d_spec,
                                     c->d_spec_flags, tq, c->d_top4_rec, s, top_ext));
         // Batch k+1's merge inside step k (default since round 5, "instep"): the sweep
-        // workgroups count themselves done on a device counter, then one wave per
-        // pod merges the tile lists (written through, read L2-bypassing across the
-        // XCDs) while the validator continues; a worker whose bounded wait runs out
-        // leaves its pods untagged and the next validation merges them itself.
+        // workgroups stamp every tile list they write with the step's tag, and one
+        // wave per pod polls the pod's lists (written through, read L2-bypassing
+        // across the XCDs) until all carry it, then merges them while the validator
+        // continues; a worker whose bounded wait runs out leaves its pods untagged
+        // and the next validation merges them itself.
         // With the binary64 tile keys the sweep + merge path fits beside the
         // validator: config E 44.4 -> 40.5 ms against the merge launch
         // (profiles/r05c_e_ab.txt, r05f_e_sync_ab.txt). MINISCHED_SEQ_MERGE=launch:
         // a k_topk_merge launch after each step (A/B); "fallback": the in-step
         // workers skip (a test hook). Read per call (tests switch it); the lists
         // were cleared above.
-        uint32_t k = 0, in_tag = 0, target = 0;
+        uint32_t k = 0, in_tag = 0;
         for (uint32_t s0 = 0, nb = 0; s0 < n_pods; s0 += nb, ++k) {
             nb = std::min(batch_at(s0), n_pods - s0);
             const uint32_t cur = k & 1u, nxt = cur ^ 1u;
             const uint32_t s1 = s0 + nb, nn = s1 < n_pods ? std::min(batch_at(s1), n_pods - s1) : 0u;
-            unsigned long long *tk = c->d_tile_keys + cells_per_set * seq_topk() * cur;
-            unsigned long long *tk1 = c->d_tile_keys + cells_per_set * seq_topk() * nxt;
-            uint32_t *tf = c->d_tile_flags + cells_per_set * cur, *tf1 = c->d_tile_flags + cells_per_set * nxt;
-            SeqMergeIO mio;
+            const size_t top_per_set = (size_t)SB * seq_topk();
+            SeqStep st;
+            st.t = tq;
+            st.n_rows = rows;
+            st.n_tiles = n_tiles;
+            st.seed32 = seed32;
+            st.num_cus = c->num_cus;
+            // batch k: validated
+            st.pods = d_pods + s0;
+            st.n_pods = nb;
+            st.tile_keys = c->d_tile_keys + cells_per_set * seq_topk() * cur;
+            st.tile_flags = c->d_tile_flags + cells_per_set * cur;
+            st.spec = c->d_spec + SB * cur;
+            st.spec_flags = c->d_spec_flags + SB * cur;
+            st.top4 = c->d_top4 + top_per_set * cur;
+            st.top4_recs = c->d_top4_rec + recs_per_set * cur;
+            st.top_ext = top_ext + top_per_set * cur;
+            st.prev_in = k ? c->d_prev + prev_words * nxt : nullptr;
+            st.prev_recs_in = k ? c->d_prev_rec + prev_fields * nxt : nullptr;
+            st.prev_out = c->d_prev + prev_words * cur;
+            st.prev_recs_out = c->d_prev_rec + prev_fields * cur;
+            st.results = d_res + s0;
+            st.stats = c->d_overflow;
+            // batch k+1: swept, and merged into the other buffer set (in the step, or by the launch below)
+            st.next_pods = nn ? d_pods + s1 : nullptr;
+            st.n_next = nn;
+            st.next_tile_keys = c->d_tile_keys + cells_per_set * seq_topk() * nxt;
+            st.next_tile_flags = c->d_tile_flags + cells_per_set * nxt;
+            unsigned long long *const top1 = c->d_top4 + top_per_set * nxt, *const spec1 = c->d_spec + SB * nxt;
+            unsigned long long *const ext1 = top_ext + top_per_set * nxt;
+            uint32_t *const spec_flags1 = c->d_spec_flags + SB * nxt;
+            int64_t *const recs1 = c->d_top4_rec + recs_per_set * nxt;
+            SeqMergeIO &mio = st.merge;
 #if defined(MS_VSTAMPS) || defined(MS_TIMELINE_ONLY)
             // diagnostic builds: timeline of steps 0 .. kTimelineSteps - 1 (MS_TIMELINE=<file>)
             static const bool want_tl = getenv("MS_TIMELINE") != nullptr;
@@ -347,35 +364,23 @@ int run_sequential(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resu
             mio.tl_step = k;
             mio.in_tags = c->d_merge_tags + SB * cur;
             mio.in_tag = in_tag;
-            mio.ctr = c->d_merge_ctr;
-            mio.target = target;
             const bool in_step = want_instep && seq_step_merges(tq, n_tiles, nn);
             if (in_step) {
                 if (++c->merge_tag == 0) ++c->merge_tag;  // (0: no tag)
-                mio.top = c->d_top4 + (size_t)SB * seq_topk() * nxt;
-                mio.spec = c->d_spec + SB * nxt;
-                mio.spec_flags = c->d_spec_flags + SB * nxt;
-                mio.recs = c->d_top4_rec + recs_per_set * nxt;
-                mio.ext = top_ext + (size_t)SB * seq_topk() * nxt;
+                mio.top = top1;
+                mio.spec = spec1;
+                mio.spec_flags = spec_flags1;
+                mio.recs = recs1;
+                mio.ext = ext1;
                 mio.tags = c->d_merge_tags + SB * nxt;
                 mio.tag = c->merge_tag;
                 mio.skip = merge_mode == "fallback" ? 1 : 0;
             }
-            MS_HIP(c, launch_seq_step(tq, rows, n_tiles, seed32, d_pods + s0, nb, tk, tf, c->d_spec + SB * cur,
-                                      c->d_spec_flags + SB * cur, c->d_top4 + (size_t)SB * seq_topk() * cur,
-                                      c->d_top4_rec + recs_per_set * cur,
-                                      k ? c->d_prev + prev_words * nxt : nullptr,
-                                      k ? c->d_prev_rec + prev_fields * nxt : nullptr, c->d_prev + prev_words * cur,
-                                      c->d_prev_rec + prev_fields * cur, d_res + s0, c->d_overflow,
-                                      nn ? d_pods + s1 : nullptr, nn, tk1, tf1, c->num_cus, s,
-                                      top_ext + (size_t)SB * seq_topk() * cur, &mio));
-            target = mio.target;
+            MS_HIP(c, launch_seq_step(st, s));
             in_tag = in_step ? mio.tag : 0u;
             if (nn && !in_step)
-                MS_HIP(c, launch_topk_merge(tk1, tf1, nn, n_tiles, c->d_top4 + (size_t)SB * seq_topk() * nxt,
-                                            c->d_spec + SB * nxt, c->d_spec_flags + SB * nxt, c->t,
-                                            c->d_top4_rec + recs_per_set * nxt, s,
-                                            top_ext + (size_t)SB * seq_topk() * nxt));
+                MS_HIP(c, launch_topk_merge(st.next_tile_keys, st.next_tile_flags, nn, n_tiles, top1, spec1, spec_flags1,
+                                            tq, recs1, s, ext1));
         }
         return MS_OK;
     }
@@ -711,13 +716,12 @@ int ensure_zc(ms_ctx *c, uint32_t n) {
 // chunk i runs. For ms_schedule_batch the pageable copies this replaces cost
 // 0.59 ms at config C (the blocking D2H alone ~0.42 ms of host time) and once
 // took 7.3 ms (BENCH_r03 e2e.runs[4]; the A/B rerun caught a 6.7 ms pageable
-// H2D in the call's stage_in phase, profiles/r04b_e2e_zc_ab.txt);
-// MINISCHED_PAGEABLE_E2E=1 restores them (A/B). Chunks: one per 50k pods, at
-// most 4. With the fixed-slot K1 (shorter kernels) config C's 100k pods in 2
+// H2D in the call's stage_in phase, profiles/r04b_e2e_zc_ab.txt).
+// Chunks: one per 50k pods, at most 4. With the fixed-slot K1 (shorter kernels) config C's 100k pods in 2
 // chunks overlap the host copies: 0.320 vs 0.328 ms compact, 0.362 vs 0.403 ms
 // with 40/24-B records (profiles/r04zb_zc_parts.txt; 3 chunks 0.325 / 0.364;
 // round 3, slot-search K1: 4 chunks of 25k cost as much kernel time as their
-// overlap saved). MINISCHED_ZC_PARTS overrides the chunk count (1..4).
+// overlap saved).
 constexpr uint32_t kZcMinChunk = 50000;
 constexpr uint32_t kZcParMin = 16384;  // pods per chunk from which the copies use the pool
 template <typename PodIn, typename ResOut>
@@ -887,46 +891,26 @@ int ms_create(const ms_config *cfg, ms_ctx **out) {
     NodeTable &t = c->t;
     t.cap = cfg->max_nodes;
     t.base = cfg->node_base;
-#ifndef MS_TABLE_ONE_ALLOC
-#define MS_TABLE_ONE_ALLOC 1
-#endif
-    bool ok;
-    if (MS_TABLE_ONE_ALLOC) {
-        // Every column in one allocation, 2 MB-rounded: the validator's write-back
-        // stores one scattered row per lane into five of them each step, and
-        // separate allocations spread those rows over many more translation entries.
-        void **cols[] = {(void **)&t.flags,     (void **)&t.digit,     (void **)&t.zone,    (void **)&t.label2,
-                         (void **)&t.taints,    (void **)&t.allowed_pods, (void **)&t.pod_count, (void **)&t.alloc_cpu,
-                         (void **)&t.alloc_mem, (void **)&t.req_cpu,   (void **)&t.req_mem, (void **)&t.nz_cpu,
-                         (void **)&t.nz_mem};
-        const size_t bytes[] = {n + kColumnPad, n + kColumnPad, n + kColumnPad, n + kColumnPad, n * 4, n * 4, n * 4,
-                                n * 8,          n * 8,          n * 8,          n * 8,          n * 8, n * 8};
-        static_assert(sizeof(cols) / sizeof(cols[0]) == sizeof(bytes) / sizeof(bytes[0]), "one size per column");
-        size_t off[sizeof(bytes) / sizeof(bytes[0])], total = 0;
-        for (size_t i = 0; i < sizeof(bytes) / sizeof(bytes[0]); ++i) {
-            off[i] = total;
-            total += (bytes[i] + 255) & ~(size_t)255;
-        }
-        total = (total + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
-        ok = hipMalloc(&c->d_table, total) == hipSuccess;
-        if (ok)
-            for (size_t i = 0; i < sizeof(bytes) / sizeof(bytes[0]); ++i)
-                *cols[i] = static_cast<char *>(c->d_table) + off[i];
-    } else {
-        ok = hipMalloc((void **)&t.flags, n + kColumnPad) == hipSuccess &&
-             hipMalloc((void **)&t.digit, n + kColumnPad) == hipSuccess &&
-             hipMalloc((void **)&t.zone, n + kColumnPad) == hipSuccess &&
-             hipMalloc((void **)&t.label2, n + kColumnPad) == hipSuccess &&
-             hipMalloc((void **)&t.taints, n * 4) == hipSuccess &&
-             hipMalloc((void **)&t.allowed_pods, n * 4) == hipSuccess &&
-             hipMalloc((void **)&t.pod_count, n * 4) == hipSuccess &&
-             hipMalloc((void **)&t.alloc_cpu, n * 8) == hipSuccess &&
-             hipMalloc((void **)&t.alloc_mem, n * 8) == hipSuccess &&
-             hipMalloc((void **)&t.req_cpu, n * 8) == hipSuccess &&
-             hipMalloc((void **)&t.req_mem, n * 8) == hipSuccess &&
-             hipMalloc((void **)&t.nz_cpu, n * 8) == hipSuccess &&
-             hipMalloc((void **)&t.nz_mem, n * 8) == hipSuccess;
+    // Every column in one allocation, 2 MB-rounded: the validator's write-back
+    // stores one scattered row per lane into five of them each step, and
+    // separate allocations spread those rows over many more translation entries.
+    void **cols[] = {(void **)&t.flags,     (void **)&t.digit,     (void **)&t.zone,    (void **)&t.label2,
+                     (void **)&t.taints,    (void **)&t.allowed_pods, (void **)&t.pod_count, (void **)&t.alloc_cpu,
+                     (void **)&t.alloc_mem, (void **)&t.req_cpu,   (void **)&t.req_mem, (void **)&t.nz_cpu,
+                     (void **)&t.nz_mem};
+    const size_t bytes[] = {n + kColumnPad, n + kColumnPad, n + kColumnPad, n + kColumnPad, n * 4, n * 4, n * 4,
+                            n * 8,          n * 8,          n * 8,          n * 8,          n * 8, n * 8};
+    static_assert(sizeof(cols) / sizeof(cols[0]) == sizeof(bytes) / sizeof(bytes[0]), "one size per column");
+    size_t off[sizeof(bytes) / sizeof(bytes[0])], total = 0;
+    for (size_t i = 0; i < sizeof(bytes) / sizeof(bytes[0]); ++i) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
     }
+    total = (total + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
+    bool ok = hipMalloc(&c->d_table, total) == hipSuccess;
+    if (ok)
+        for (size_t i = 0; i < sizeof(bytes) / sizeof(bytes[0]); ++i)
+            *cols[i] = static_cast<char *>(c->d_table) + off[i];
     t.gcap = (uint32_t)((n + kGroupRows - 1) / kGroupRows);
     ok = ok && hipMalloc((void **)&t.planes, sizeof(uint32_t) * kPlanes * t.gcap) == hipSuccess;
     if (!ok) return bail(MS_E_OOM, "node table allocation");

@@ -72,7 +72,6 @@ struct ms_ctx {
     int64_t *d_top4_rec = nullptr;         // their batch-start node records (validator layout)
     unsigned long long *d_top_ext = nullptr;  // ranks 4..7 per pod (the validator's slow pods)
     uint32_t *d_merge_tags = nullptr;         // per pod of both merge-output sets: the in-step merge's tag
-    uint32_t *d_merge_ctr = nullptr;          // the in-step merge's sweep-done counter
     void *d_table = nullptr;                  // the node table's columns, one allocation (ms_create)
     uint32_t merge_tag = 0;                   // last in-step merge tag issued
     unsigned long long *d_tl = nullptr;       // MS_VSTAMPS: step timeline (MS_TIMELINE=<file> dumps it at ms_destroy)
@@ -210,8 +209,8 @@ void comm_rank_world(const ms_ctx *c, int32_t *rank, int32_t *world);
 // communicator's internal streams; returns 1 if it inserted waits, 0 if none
 // were outstanding (or no communicator), < 0 on failure.
 int comm_fence_reads(ms_ctx *c, hipStream_t writer);
-// MS_PLUGINS_NU_TT_NN: the two-pass bit-sliced cycle (default) or, with
-// MINISCHED_TT=v1, the per-pair summary sweep (read once per process).
+// MS_PLUGINS_NU_TT_NN scratch of at least `need` bytes (the two-pass bit-sliced
+// cycle's, or the node shards' summaries).
 int ensure_tt(ms_ctx *c, size_t need);
 
 }  // namespace msgpu

@@ -1,5 +1,6 @@
 // ms_device.h — device helpers shared by the kernel translation units
-// (ms_kernels.hip, ms_sweep_pp.hip). Not part of the public boundary.
+// (ms_kernels.hip, ms_seq.hip, ms_sweep_pp.hip, ms_taint.hip, ms_affinity.hip).
+// Not part of the public boundary.
 #pragma once
 
 #include "ms_internal.h"
@@ -40,6 +41,33 @@ __device__ __forceinline__ uint32_t wave_max_u32_dpp(uint32_t v) {
     v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false));  // row_bcast:15
     v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false));  // row_bcast:31
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// 64-bit unsigned wave max by butterfly shuffles; every lane gets it.
+__device__ __forceinline__ u64 wave_max_u64(u64 v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = umax64(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// 64-bit unsigned wave max from two DPP u32 reductions; wave-uniform result.
+__device__ __forceinline__ u64 wave_max_u64_dpp(u64 v) {
+    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
+    const uint32_t hmax = wave_max_u32_dpp(hi);
+    const uint32_t lmax = wave_max_u32_dpp(hi == hmax ? lo : 0u);
+    return ((u64)hmax << 32) | lmax;
+}
+
+// wave_max_u64_dpp where one lane usually holds the high-word maximum (the
+// sweep's packed keys): that lane supplies the low word by one readlane
+// instead of a second reduction.
+__device__ __forceinline__ u64 wave_max_u64_unique(u64 v) {
+    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
+    const uint32_t hmax = wave_max_u32_dpp(hi);
+    const u64 tie = __ballot(hi == hmax);
+    if ((tie & (tie - 1ull)) == 0ull)
+        return ((u64)hmax << 32) | (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)__builtin_ctzll(tie));
+    return ((u64)hmax << 32) | wave_max_u32_dpp(hi == hmax ? lo : 0u);
 }
 
 // Per-lane maximum of 8 registers, reduced over the wave; pod j's maximum

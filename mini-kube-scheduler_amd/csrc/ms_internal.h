@@ -66,7 +66,7 @@ __host__ __device__ inline uint32_t tile_rows_of(const NodeTable &t) {
 }
 
 // One node as the config-E sweep's binary64 LeastAllocated form reads it
-// (ms_kernels.hip make_drow; 64 B, one row per lane and load).
+// (ms_rows.h make_drow; 64 B, one row per lane and load).
 struct DRow {
     int64_t fr_cpu, fr_mem;  // Allocatable - Requested (NodeResourcesFit)
     double r_cpu, r_mem;     // RN(100 / Allocatable), 0 when Allocatable <= 0
@@ -245,6 +245,24 @@ hipError_t launch_decode_na(const ms_pod_rec *pods, uint32_t n_pods, const unsig
 hipError_t launch_sweep_full(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
                              uint32_t seed32, unsigned long long *keys, uint32_t *flags, int num_cus,
                              hipStream_t s);
+// Derived rows [0, n_total) of the sequential engine's table copy (t.drow): rows
+// at or past n_rows are absent.
+hipError_t launch_build_drows(const NodeTable &t, uint32_t n_rows, uint32_t n_total, hipStream_t s);
+// present_dev (optional): read the present count from the device (node-sharded combine)
+hipError_t launch_decode(const ms_pod_rec *pods, uint32_t n_pods, const unsigned long long *keys,
+                         const uint32_t *flags, uint32_t present_nodes, ms_result *out, hipStream_t s,
+                         const uint32_t *present_dev = nullptr);
+
+// ---- the exact sequential engine's launchers (ms_seq.hip) ------------------
+// Largest speculative batch the sequential validator accepts.
+uint32_t seq_batch_limit();
+// i64 fields per validator node record; stale nodes per prev list.
+uint32_t seq_rec_fields();
+uint32_t seq_prev_cap();
+// Entries per (pod, tile) speculative list: tile_keys has n_pods * n_tiles * seq_topk() u64.
+uint32_t seq_topk();
+// Rows the sequential engine's validator supports (tile lists held in registers).
+uint32_t seq_max_rows();
 // Per-(pod, wave tile) speculative sweep for the sequential engine: the
 // tile's top-K keys at tile_keys[(p * n_tiles + t) * K + j], 0-terminated,
 // and its filter flags at tile_flags[p * n_tiles + t].
@@ -264,22 +282,23 @@ hipError_t launch_topk_merge(const unsigned long long *tile_keys, const uint32_t
                              uint32_t n_tiles, unsigned long long *top, unsigned long long *spec, uint32_t *spec_flags,
                              const NodeTable &t, int64_t *recs, hipStream_t s, unsigned long long *ext = nullptr);
 // Batch k+1's merge inside step k at depth 1 (MINISCHED_SEQ_MERGE=instep):
-// once every sweep workgroup of the step has written batch k+1's tile lists
-// (write-through stores, counted on ctr), their waves merge its pods into these
+// the step's sweep workgroups write batch k+1's tile lists through, each list
+// stamped with the step's 2-bit tag (derived from `tag`), and their waves poll
+// the lists until every one carries it, then merge the batch's pods into these
 // buffers (launch_topk_merge's outputs), tagging each merged pod with `tag`.
+// The lists must hold no tag of an earlier run (zeroed at the run's start).
 // The wait is bounded: a worker that gives up leaves its pods untagged and
 // validation k+1 merges them itself, so a grid that is not co-resident costs
-// time, never correctness. ctr: a u32 zeroed at the run's start; target: the
-// count after the run's earlier in-step merges, advanced by launch_seq_step.
+// time, never correctness. top == nullptr: no in-step merge.
 // in_tags / in_tag: batch k's tags (in_tag 0: batch k was merged by a launch).
 // skip: the workers leave every pod to the fallback (a test hook).
 struct SeqMergeIO {
     const uint32_t *in_tags = nullptr;
     uint32_t in_tag = 0;
     unsigned long long *top = nullptr, *spec = nullptr, *ext = nullptr;
-    uint32_t *spec_flags = nullptr, *tags = nullptr, *ctr = nullptr;
+    uint32_t *spec_flags = nullptr, *tags = nullptr;
     int64_t *recs = nullptr;
-    uint32_t tag = 0, target = 0;
+    uint32_t tag = 0;
     int skip = 0;
     // MS_VSTAMPS diagnostic build: per-workgroup timestamps of steps
     // tl_step < kTimelineSteps (u64 [step][workgroup][8], s_memrealtime)
@@ -291,21 +310,43 @@ constexpr uint32_t kTimelineSteps = 2048, kTimelineWgs = 256;  // (a config E ru
 bool seq_step_merges(const NodeTable &t, uint32_t n_tiles, uint32_t n_next);
 // One single-stream step: in-order validation of batch k (n_pods, workgroup 0;
 // writes results and commits binds to the table) while sweeping the next batch
-// (n_next pods: tile lists, and with mio their in-step merge; else
-// launch_topk_merge follows the step). prev_in / prev_recs_in: the stale nodes
-// (bound by the previous batch) with their final records ({n_own, n_carried,
-// rows} of 2 + seq_prev_cap() words; seq_prev_cap() * seq_rec_fields() i64),
-// written by the previous validation into its prev_out / prev_recs_out.
-// stats: u32[6] = overflow flags, re-swept tiles, recomputed entries, pods,
-// speculation misses, pods whose speculative winner was touched. Any count may be 0.
-hipError_t launch_seq_step(const NodeTable &t, uint32_t n_rows, uint32_t n_tiles, uint32_t seed32,
-                           const ms_pod_rec *pods, uint32_t n_pods, const unsigned long long *tile_keys,
-                           const uint32_t *tile_flags, const unsigned long long *spec, const uint32_t *spec_flags,
-                           const unsigned long long *top4, const int64_t *top4_recs, const uint32_t *prev_in,
-                           const int64_t *prev_recs_in, uint32_t *prev_out, int64_t *prev_recs_out,
-                           ms_result *results, uint32_t *stats, const ms_pod_rec *next_pods, uint32_t n_next,
-                           unsigned long long *next_tile_keys, uint32_t *next_tile_flags, int num_cus,
-                           hipStream_t s, const unsigned long long *top_ext = nullptr, SeqMergeIO *mio = nullptr);
+// (n_next pods: tile lists, and with merge.top their in-step merge; else
+// launch_topk_merge follows the step). Either count may be 0.
+struct SeqStep {
+    NodeTable t;
+    uint32_t n_rows = 0, n_tiles = 0, seed32 = 0;
+    int num_cus = 0;
+    // batch k, validated: its pods, tile lists and launch_topk_merge's outputs
+    // (top_ext: ranks 4..7, optional)
+    const ms_pod_rec *pods = nullptr;
+    uint32_t n_pods = 0;
+    const unsigned long long *tile_keys = nullptr;
+    const uint32_t *tile_flags = nullptr;
+    const unsigned long long *spec = nullptr;
+    const uint32_t *spec_flags = nullptr;
+    const unsigned long long *top4 = nullptr;
+    const int64_t *top4_recs = nullptr;
+    const unsigned long long *top_ext = nullptr;
+    // prev_in / prev_recs_in: the stale nodes (bound by the previous batch) with
+    // their final records ({n_own, n_carried, rows} of 2 + seq_prev_cap() words;
+    // seq_prev_cap() * seq_rec_fields() i64), written by the previous validation
+    // into its prev_out / prev_recs_out. prev_in null: the sweep saw every earlier bind.
+    const uint32_t *prev_in = nullptr;
+    const int64_t *prev_recs_in = nullptr;
+    uint32_t *prev_out = nullptr;
+    int64_t *prev_recs_out = nullptr;
+    ms_result *results = nullptr;
+    // u32[6] = overflow flags, re-swept tiles, recomputed entries, pods,
+    // speculation misses, pods whose speculative winner was touched
+    uint32_t *stats = nullptr;
+    // batch k+1, swept: its pods and the tile lists written
+    const ms_pod_rec *next_pods = nullptr;
+    uint32_t n_next = 0;
+    unsigned long long *next_tile_keys = nullptr;
+    uint32_t *next_tile_flags = nullptr;
+    SeqMergeIO merge;
+};
+hipError_t launch_seq_step(const SeqStep &a, hipStream_t s);
 // Node-sharded sequential mode (minisched_gpu.h ms_seq_*): this shard's top-4
 // candidates with records + all-tile filter flags per pod, from the top-4 merge
 // output; and the replicated validation over the shards' gathered lists
@@ -320,19 +361,12 @@ hipError_t launch_seq_validate_rep(const NodeTable &t, uint32_t n_pods, const ms
 // Device cursor of the in-library node-sharded sequential cycle: ctl = {cursor,
 // live, n_done}; window_in stages pods [cursor, cursor + live) of n into win (w
 // entries), window_out copies ctl[2] decided results to res[cursor ..] and
-// advances the cursor (ms_kernels.hip).
+// advances the cursor.
 hipError_t launch_seq_window_in(const ms_pod_rec *pods, uint32_t n, uint32_t *ctl, ms_pod_rec *win, uint32_t w,
                                 hipStream_t s);
 hipError_t launch_seq_window_out(const ms_result *win_res, uint32_t *ctl, ms_result *res, uint32_t n, hipStream_t s);
-// Derived rows [0, n_total) of the sequential engine's table copy (t.drow): rows
-// at or past n_rows are absent.
-hipError_t launch_build_drows(const NodeTable &t, uint32_t n_rows, uint32_t n_total, hipStream_t s);
-// Rows the sequential engine's validator supports (tile lists held in registers).
-uint32_t seq_max_rows();
-// present_dev (optional): read the present count from the device (node-sharded combine)
-hipError_t launch_decode(const ms_pod_rec *pods, uint32_t n_pods, const unsigned long long *keys,
-                         const uint32_t *flags, uint32_t present_nodes, ms_result *out, hipStream_t s,
-                         const uint32_t *present_dev = nullptr);
+
+// ---- MS_PLUGINS_NU_TT_NN launchers (ms_taint.hip) --------------------------
 // MS_PLUGINS_NU_TT_NN (ms_taint.hip): per-pod summaries of LIST-ordered row
 // segments (tt_segments(n_rows) of them, segment s at summaries[s * n_pods + p],
 // MS_TT_SUMMARY_BYTES each), and their merge: n_segs summaries per pod (segment
@@ -371,6 +405,8 @@ hipError_t launch_tt2_final_shard(const NodeTable &t, uint32_t n_rows, const ms_
 hipError_t launch_tt_combine(const void *in, uint32_t stride, uint32_t n_segs, const ms_pod_rec *pods, uint32_t n_pods,
                              uint32_t seed32, void *out, ms_result *results, const NodeTable &t, int commit,
                              hipStream_t s);
+
+// ---- launchers (ms_kernels.hip), continued: decodes, binds, read-back ------
 // One launch decoding several batches' pod slices, each with a device-side present flag.
 constexpr uint32_t kMaxSliceJobs = 8;
 struct SliceJob {
@@ -393,12 +429,5 @@ hipError_t launch_read_rows(const NodeTable &t, uint32_t first, uint32_t n, ms_n
 // requests), results narrowed to ms_result_compact, on the device.
 hipError_t launch_pods_widen(const ms_pod_compact *in, uint32_t n, ms_pod_rec *out, hipStream_t s);
 hipError_t launch_results_narrow(const ms_result *in, uint32_t n, ms_result_compact *out, hipStream_t s);
-// Largest speculative batch the sequential validator accepts.
-uint32_t seq_batch_limit();
-// i64 fields per validator node record; stale nodes per prev list.
-uint32_t seq_rec_fields();
-uint32_t seq_prev_cap();
-// Entries per (pod, tile) speculative list: tile_keys has n_pods * n_tiles * seq_topk() u64.
-uint32_t seq_topk();
 
 }  // namespace msgpu

@@ -62,12 +62,7 @@ constexpr uint32_t truth3(F f) {  // v_bitop3 table, S0 the most significant ind
 constexpr uint32_t kXnorAnd = truth3([](int a, int b, int c) { return c && a == b; });  // c & ~(a ^ b)
 constexpr uint32_t kSelect = truth3([](int a, int b, int c) { return c ? a : b; });     // c ? a : b
 
-#ifndef MS_TAIL_PACK
-#define MS_TAIL_PACK 1  // (0: the last partial word as a full one, A/B)
-#endif
-#ifndef MS_TAIL_SHARE
-#define MS_TAIL_SHARE 4  // waves sharing the packed last word (A/B)
-#endif
+constexpr uint32_t kTailShare = 4;  // waves sharing the packed last word (tail_pods)
 
 constexpr int kPpWords = 4;      // 30-row groups per lane (KW, shards above kPpSmallGroups)
 constexpr int kPpWordsSmall = 8; // KW for small shards: one wave holds every row
@@ -336,7 +331,7 @@ __device__ __forceinline__ void sweep_range(const Word (&W)[KW], const Word &Wt,
 // sixteenths, with and without it (100,000 rows over 16 waves: 14 -> 13.06;
 // 50,010 over 8: 7 either way, and packing cost 1 %).
 __host__ __device__ inline uint32_t tail_pods(uint32_t ng, uint32_t waves) {
-    if (!MS_TAIL_PACK || ng == 0) return 0u;
+    if (ng == 0) return 0u;
     const uint32_t wlast = (ng + 63u) / 64u - 1u, tail_n = ng - wlast * 64u;
     // (8 pods per evaluation only: 2 per evaluation, 17 groups left over a
     // 6,250-row wave, cost more than the full word, profiles/r03zk_tail_pack_ab.txt)
@@ -347,7 +342,7 @@ __host__ __device__ inline uint32_t tail_pods(uint32_t ng, uint32_t waves) {
     // word saved is saved on every SIMD
     if (waves <= 4u) return tpt;
     const uint32_t wv_t = wlast % waves;
-    const uint32_t tshare = (uint32_t)MS_TAIL_SHARE < waves - wv_t ? (uint32_t)MS_TAIL_SHARE : waves - wv_t;
+    const uint32_t tshare = kTailShare < waves - wv_t ? kTailShare : waves - wv_t;
     uint32_t L[4] = {0, 0, 0, 0};
     for (uint32_t w = 0; w < waves && w <= wlast; ++w) L[w & 3u] += 16u * ((wlast - w) / waves + 1u);
     auto mx = [&] {
@@ -407,7 +402,7 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     const uint32_t ng = min(n_groups - g0, waves * 64u * KW);  // (blockIdx.y < gy: g0 < n_groups)
     const uint32_t wlast = (ng + 63u) / 64u - 1u, tail_n = ng - wlast * 64u;
     uint32_t tpt = TP ? tail_pods(ng, waves) : 0u;
-    const uint32_t wv_t = wlast % waves, tshare = min((uint32_t)MS_TAIL_SHARE, waves - wv_t);  // its waves
+    const uint32_t wv_t = wlast % waves, tshare = min(kTailShare, waves - wv_t);  // its waves
     const bool owner = wv == wv_t;     // it is this wave's last word in the dealing
     if (wv < wv_t || wv >= wv_t + tshare) tpt = 0u;  // wave-uniform
     Word W[KW], Wt;
@@ -449,7 +444,7 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
         over = over || (in && (planes[kPlaneOver * gstride + g] & 1u) != 0u);
     }
     const bool gen = __ballot(over) != 0;
-    // every word of the wave digit-aligned (MINISCHED_PP_FIX=0 at launch: never)
+    // every word of the wave digit-aligned
     const int mode = gen ? kModeGen : (fix_ok && __ballot(misaligned) == 0) ? kModeFix : kModeFast;
     __syncthreads();
     if (np && (nw || tpt)) {
@@ -584,7 +579,6 @@ hipError_t launch_build_planes(const NodeTable &t, const NodeDelta *d_deltas, ui
 // rows: grid.y workgroups per chunk); pods per workgroup sized for one
 // round of resident workgroups (16 waves per CU while chunks stay <= 1024
 // pods, else 32) in multiples of 8, at most kPpMaxChunk (LDS).
-// MINISCHED_PP_CHUNK overrides the chunk (tuning).
 constexpr uint32_t kPpMaxChunk = 2048;
 
 namespace {

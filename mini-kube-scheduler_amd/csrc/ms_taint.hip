@@ -31,10 +31,7 @@ namespace {
 
 constexpr int kTtClasses = 18;  // c in 0..8 x rank parity
 constexpr uint32_t kTtThreads = 256;   // pods per sweep workgroup (one per lane)
-#ifndef MS_TT_TILE
-#define MS_TT_TILE 1024
-#endif
-constexpr uint32_t kTtTile = MS_TT_TILE;  // rows staged in LDS per pass (2048 -> 1024: 8.24 -> 6.92 ms at 50k x 100k)
+constexpr uint32_t kTtTile = 1024;  // rows staged in LDS per pass (2048 -> 1024: 8.24 -> 6.92 ms at 50k x 100k)
 constexpr uint32_t kTtSegRows = 2048;  // minimum rows per segment
 constexpr uint32_t kTtMaxSegs = 16;
 constexpr uint32_t kTtCombineThreads = 128;  // k_tt_combine: one pod per thread, its running summary in LDS

@@ -1,5 +1,5 @@
 /* Exactness of the binary64 LeastAllocated fast form used by the config-E sweep
- * (ms_kernels.hip, la_fast): for 0 <= cap < 2^41, av <= cap, 0 <= n < 2^53,
+ * (ms_rows.h, la_r / la_a / eval_fast): for 0 <= cap < 2^41, av <= cap, 0 <= n < 2^53,
  *   r  = RN(100 / cap)            (0 when cap <= 0)
  *   a2 = RN(RN(av * r) + 2^-43)
  *   x  = RN(-n * r + a2)          (one fused multiply-add)

@@ -449,9 +449,13 @@ def test_resource_sequential_merge_forms(oracle, monkeypatch, batch, merge):
             assert e.info()._pad == 0
 
 
-@pytest.mark.parametrize("n_nodes", [20_000, 100_000, 140_000])
+@pytest.mark.parametrize("n_nodes", [6_000, 20_000, 100_000, 140_000])
 def test_resource_sequential_tile_counts(oracle, n_nodes):
-    # validator register layouts for 79, 391 and 547 tiles (2, 8 and 16 lists per lane)
+    # validator and merge register layouts for 2, 4, 8 and 16 tile lists per lane (65..128,
+    # ..256, ..512, ..1024 tiles). Tiles are sized to the CUs: rows per tile =
+    # clamp(roundup16(ceil(rows / (CUs - 1))), 64, 256), so on a 256-CU part 6,000 nodes give
+    # 94 tiles of 64 rows, 20,000 give 250 of 80, 100,000 give 391 and 140,000 give 547 of 256.
+    # (One list per lane, up to 64 tiles: every sequential test below 4,097 nodes.)
     nr = synth.nodes(n_nodes, seed=5, resources=True)
     pr = synth.pods(1500, seed=5, resources=True)
     o = oracle.schedule(nr, pr, plugin_set=1, mode=1, seed=5)

@@ -1,4 +1,4 @@
-"""The config-E sweep's binary64 LeastAllocated form (ms_kernels.hip la_r /
+"""The config-E sweep's binary64 LeastAllocated form (ms_rows.h la_r /
 la_a / eval_fast) equals the reference's integer leastRequestedScore on every
 boundary case tests/c/la_f64_exact.c generates (CPU; the GPU parity suite runs
 the kernel itself, tests/test_gpu_parity.py::test_resource_sequential_capacity_forms)."""

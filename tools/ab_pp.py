@@ -45,7 +45,7 @@ def main():
     base_ord = int(os.environ.get("AB_NODE_BASE", 0))
     rounds = int(os.environ.get("AB_ROUNDS", 8))
     mode = os.environ.get("AB_MODE", "select")
-    variants = parse_variants(os.environ.get("AB_VARIANTS", "pp:MINISCHED_K1=pp"))
+    variants = parse_variants(os.environ.get("AB_VARIANTS", "default:"))
     touched = {k for _, env in variants for k in env}
     base_env = {k: os.environ.get(k) for k in touched}
     dev = torch.device("cuda:0")

@@ -1,7 +1,6 @@
 """The TT extension config alone (bench.py's `configs.TT`: 50k nodes x 100k
 pods, MS_PLUGINS_NU_TT_NN, batched, device entry point): median of --reps timed
-cycles and the oracle's closed form on a 2,000-pod prefix (checker). For A/Bs:
-MINISCHED_TT=v1 selects the per-pair summary sweep."""
+cycles and the oracle's closed form on a 2,000-pod prefix (checker)."""
 import argparse
 import json
 import os
@@ -45,5 +44,5 @@ import _oracle  # noqa: E402  (checker)
 o = _oracle.schedule_tt(nr, pr[:2000], literal=False, seed=args.seed)
 ok = all(np.array_equal(got[k][:2000].astype(np.int64), o[ko].astype(np.int64))
          for k, ko in (("node", "node"), ("code", "code"), ("score", "score"), ("plugin_mask", "mask")))
-print(json.dumps({"tt": os.environ.get("MINISCHED_TT", "v2"), "median_ms": float(np.median(ts)) * 1e3,
+print(json.dumps({"median_ms": float(np.median(ts)) * 1e3,
                   "runs_ms": [t * 1e3 for t in ts], "evals_per_s": N * P / float(np.median(ts)), "parity_prefix": ok}))

@@ -1,5 +1,5 @@
-"""Config E against its golden fixture under the current environment (warm-up
-batches / merge form); prints the mismatch count and the first differing pods."""
+"""Config E against its golden fixture under the current environment (the merge
+form, MINISCHED_SEQ_MERGE); prints the mismatch count and the first differing pods."""
 import json
 import os
 import sys
@@ -20,6 +20,6 @@ for rep in range(int(os.environ.get("REPS", "2"))):
         r = e.schedule(pr, _lib.MODE_SEQUENTIAL)
         dt = time.perf_counter() - t0
     bad = np.nonzero(r["node"].astype(np.int64) != fx["node"].astype(np.int64))[0]
-    print(json.dumps({"warm": os.environ.get("MINISCHED_SEQ_WARM"), "merge": os.environ.get("MINISCHED_SEQ_MERGE"),
+    print(json.dumps({"merge": os.environ.get("MINISCHED_SEQ_MERGE"),
                       "rep": rep, "ms": round(dt * 1e3, 2), "n_bad": int(len(bad)),
                       "first": bad[:6].tolist()}), flush=True)

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """ms_schedule_batch_compact at config C (100k nodes x 100k pods, host arrays):
-median wall time of 21 calls and a digest of the results (MINISCHED_COMPACT_ZC
-selects the zero-copy or the staged form; run one process per form)."""
+median wall time of 21 calls and a digest of the results."""
 import hashlib
 import json
 import os
@@ -30,7 +29,7 @@ def main():
             t0 = time.perf_counter()
             e.schedule_compact(pods, _lib.MODE_BATCHED, out=out)
             ts.append(time.perf_counter() - t0)
-    print(json.dumps({"zc": os.environ.get("MINISCHED_COMPACT_ZC", "1"), "ms_median": round(float(np.median(ts)) * 1e3, 4),
+    print(json.dumps({"ms_median": round(float(np.median(ts)) * 1e3, 4),
                       "ms_min": round(min(ts) * 1e3, 4), "digest_first_call": digest}), flush=True)
 
 

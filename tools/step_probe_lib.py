@@ -31,18 +31,14 @@ def main():
     s = torch.cuda.Stream(device=dev)
     pods = torch.from_numpy(synth.pods(P, seed=1).view(np.uint8).copy()).to(dev)
     out = {}
-    # PROBE_VARIANTS "prio:streams,...": MINISCHED_SWEEP_PRIO x MINISCHED_SHARD_STREAMS
-    variants = os.environ.get("PROBE_VARIANTS", "")
-    variants = [v.split(":") for v in variants.split(",")] if variants else \
-        [("1", st) for st in os.environ.get("PROBE_STREAMS", "2,1").split(",")]
+    # PROBE_STREAMS "2,1": MINISCHED_SHARD_STREAMS per variant
     # PROBE_COALESCE "1,0": MINISCHED_SHARD_COALESCE per variant (two submits' sweeps in one launch)
     coal = os.environ.get("PROBE_COALESCE", "1").split(",")
-    variants = [(p_, st, co) for p_, st in variants for co in coal]
-    for prio, streams, co in variants * int(os.environ.get("PROBE_REPEAT", "1")):
+    variants = [(st, co) for st in os.environ.get("PROBE_STREAMS", "2,1").split(",") for co in coal]
+    for streams, co in variants * int(os.environ.get("PROBE_REPEAT", "1")):
         os.environ["MINISCHED_SHARD_STREAMS"] = streams
         os.environ["MINISCHED_SHARD_COALESCE"] = co
-        os.environ["MINISCHED_SWEEP_PRIO"] = prio
-        streams = f"{streams}p{prio}" + ("" if co == "1" else "c0")
+        streams += "" if co == "1" else "c0"
         for G in [int(g) for g in os.environ.get("PROBE_G", "1,2,4,8,16").split(",")]:
             lo, hi = sharded.shard_bounds(N, G - 1, G)
             eng = _lib.Engine(max_nodes=hi - lo, node_base=lo, seed=1)
