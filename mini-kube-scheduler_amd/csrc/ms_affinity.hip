@@ -47,6 +47,7 @@
 #include <algorithm>
 
 #include "ms_device.h"
+#include "ms_nam_layout.h"
 
 namespace msgpu {
 
@@ -58,16 +59,15 @@ constexpr uint32_t kNamTabStride = 548;  // bytes per lane term table in LDS: 13
 constexpr uint32_t kNamComposeThreads = 128;
 constexpr uint32_t kNamClsThreads = 1024;
 constexpr uint32_t kNamPickRows = 32;  // rows per k_nam_pick step: two 16-B loads of F and two of the digit mask
-constexpr uint32_t kNamSortCap = 65536;  // (class, digit) buckets the class sort takes (else batch order)
 constexpr uint32_t kNamPickParts = 4;    // row parts per pod in a k_nam_pick workgroup (one per wave)
-constexpr uint32_t kNamDigits = 11;      // node name digit 0..9, 10 = none
+// (kNamDigits, kNamSortCap: ms_nam_layout.h, they shape the scratch)
 
 struct NamSeg {
     uint8_t T[101];  // the composed rescale map on 0..100
     uint8_t any;     // a feasible node of the segment has a non-zero raw score
     uint8_t _pad[2];
 };
-static_assert(sizeof(NamSeg) == MS_NAM_SEG_BYTES, "NamSeg layout");
+static_assert(sizeof(NamSeg) == MS_NAM_SEG_BYTES && kNamSegBytes == MS_NAM_SEG_BYTES, "NamSeg layout");
 static_assert(sizeof(NamTab) == 544 && kNamTabStride >= sizeof(NamTab), "NamTab layout");
 
 // Row word staged in LDS: bit 0 absent, bit 1 unschedulable, zone << 8,
@@ -621,66 +621,33 @@ __global__ void k_nam_dmask(NodeTable t, uint32_t n_rows, uint32_t fpitch, uint8
 
 inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
-}  // namespace
-
-// Row segments for the per-class passes: enough (segment, class-block) waves to
-// spread over the chip, 64-row multiples (F is written four rows per word and
-// read sixteen per load; a segment never writes its neighbour's rows).
-NamLayout nam_layout(uint32_t n_rows, uint32_t cls_max) {
-    NamLayout L;
-    const uint32_t blocks = std::max(1u, cdiv(cls_max, 64u));
-    // (per class and segment: rows / segs row steps, and up to segs compositions of
-    // the later segments' 101-entry tables, so a few tens of segments)
-    uint32_t segs = std::min(32u, std::max(8u, cdiv(128u, blocks)));
-    L.seg_rows = std::max(64u, cdiv(cdiv(std::max(n_rows, 1u), segs), 64u) * 64u);
-    L.segs = std::max(1u, cdiv(std::max(n_rows, 1u), L.seg_rows));
-    L.fpitch = cdiv(std::max(n_rows, 1u), 64u) * 64u;
-    L.cls_max = cls_max;
-    return L;
-}
-
-namespace {
+// The chunk's scratch arrays at ms_nam_layout.h's offsets (nam_carve_offsets:
+// the one statement of the carve, which sizes the allocation too).
 struct NamScratch {
     NamSeg *local, *comp;
     uint8_t *F, *dmask;
     uint32_t *fmax, *used, *ctl, *cls_key, *rep, *pcls, *perm, *bcnt, *bstart;
 };
-NamScratch nam_carve(void *scratch, const NamLayout &L, uint32_t n_pods, uint32_t n_sets, size_t *bytes = nullptr) {
+NamScratch nam_carve(void *scratch, const NamLayout &L, uint32_t n_pods, uint32_t n_sets) {
     char *b = static_cast<char *>(scratch);
+    const NamCarve o = nam_carve_offsets(L, n_pods, n_sets);
     NamScratch x;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char *p = b + o;
-        o += (bytes + 255u) & ~size_t(255);
-        return p;
-    };
-    x.local = reinterpret_cast<NamSeg *>(take((size_t)L.segs * L.cls_max * sizeof(NamSeg)));
-    x.comp = reinterpret_cast<NamSeg *>(take((size_t)L.cls_max * sizeof(NamSeg)));
-    x.F = reinterpret_cast<uint8_t *>(take((size_t)L.cls_max * L.fpitch));
-    x.dmask = reinterpret_cast<uint8_t *>(take((size_t)kNamDigits * L.fpitch));
-    x.fmax = reinterpret_cast<uint32_t *>(take((size_t)L.cls_max * kNamDigits * 4));
-    x.used = reinterpret_cast<uint32_t *>(take(2ull * (n_sets + 1u) * 4));
-    x.ctl = reinterpret_cast<uint32_t *>(take(16 * 4));
-    x.cls_key = reinterpret_cast<uint32_t *>(take((size_t)L.cls_max * 4));
-    x.rep = reinterpret_cast<uint32_t *>(take((size_t)L.cls_max * 4));
-    x.pcls = reinterpret_cast<uint32_t *>(take((size_t)n_pods * 4));
-    x.perm = reinterpret_cast<uint32_t *>(take((size_t)n_pods * 4));
-    const size_t nb = std::min<size_t>((size_t)L.cls_max * kNamDigits, kNamSortCap);
-    x.bcnt = reinterpret_cast<uint32_t *>(take(nb * 4));
-    x.bstart = reinterpret_cast<uint32_t *>(take(nb * 4));
-    if (bytes) *bytes = o;
+    x.local = reinterpret_cast<NamSeg *>(b + o.local);
+    x.comp = reinterpret_cast<NamSeg *>(b + o.comp);
+    x.F = reinterpret_cast<uint8_t *>(b + o.F);
+    x.dmask = reinterpret_cast<uint8_t *>(b + o.dmask);
+    x.fmax = reinterpret_cast<uint32_t *>(b + o.fmax);
+    x.used = reinterpret_cast<uint32_t *>(b + o.used);
+    x.ctl = reinterpret_cast<uint32_t *>(b + o.ctl);
+    x.cls_key = reinterpret_cast<uint32_t *>(b + o.cls_key);
+    x.rep = reinterpret_cast<uint32_t *>(b + o.rep);
+    x.pcls = reinterpret_cast<uint32_t *>(b + o.pcls);
+    x.perm = reinterpret_cast<uint32_t *>(b + o.perm);
+    x.bcnt = reinterpret_cast<uint32_t *>(b + o.bcnt);
+    x.bstart = reinterpret_cast<uint32_t *>(b + o.bstart);
     return x;
 }
 
-}  // namespace
-
-size_t nam_scratch_bytes(const NamLayout &L, uint32_t n_pods, uint32_t n_sets) {
-    size_t o = 0;
-    (void)nam_carve(nullptr, L, n_pods, n_sets, &o);
-    return o;
-}
-
-namespace {
 hipError_t nam_classes_and_segs(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
                                 const void *sets, uint32_t n_sets, const NamLayout &L, const NamScratch &x,
                                 hipStream_t s) {
@@ -708,7 +675,7 @@ hipError_t launch_nam_segment(const NodeTable &t, uint32_t n_rows, const ms_pod_
                               const void *sets, uint32_t n_sets, const NamLayout &L, void *scratch, void *out,
                               hipStream_t s) {
     if (n_pods == 0) return hipSuccess;
-    if (n_pods > L.cls_max && L.cls_max < 2u * (n_sets + 1u)) return hipErrorInvalidValue;
+    if (!nam_launch_ok(L, n_pods, n_sets)) return hipErrorInvalidValue;
     const NamScratch x = nam_carve(scratch, L, n_pods, n_sets);
     hipError_t e = nam_classes_and_segs(t, n_rows, pods, n_pods, sets, n_sets, L, x, s);
     if (e != hipSuccess) return e;
@@ -741,7 +708,7 @@ hipError_t launch_nam_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec
                            const void *after, const uint8_t *m_in, uint32_t listed, const NamLayout &L,
                            void *scratch, unsigned long long *keys, hipStream_t s) {
     if (n_pods == 0) return hipSuccess;
-    if (n_pods > L.cls_max && L.cls_max < 2u * (n_sets + 1u)) return hipErrorInvalidValue;
+    if (!nam_launch_ok(L, n_pods, n_sets)) return hipErrorInvalidValue;
     const NamScratch x = nam_carve(scratch, L, n_pods, n_sets);
     hipError_t e = nam_classes_and_segs(t, n_rows, pods, n_pods, sets, n_sets, L, x, s);
     if (e != hipSuccess) return e;

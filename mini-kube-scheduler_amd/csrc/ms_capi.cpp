@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ms_ctx.h"
+#include "ms_nam_layout.h"
 
 using namespace msgpu;
 
@@ -467,31 +468,21 @@ int tt_summaries_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, vo
     return tt_cycle_locked(c, n_pods, d_pods, out, nullptr, 0, s);
 }
 
-// MS_PLUGINS_NU_NN_NAM: pods per chunk and the per-class passes' layout. A chunk
-// holds at most min(pods, 2 (n_sets + 1)) classes, and the per-class scores F
-// take classes x rows bytes: chunks shrink so F stays within kNamFBudget (only
-// with very many term sets; 64 sets at 50k rows: 130 classes, 6.5 MB).
-constexpr size_t kNamFBudget = 512ull << 20;
-
-uint32_t nam_chunk(const ms_ctx *c, uint32_t n_pods) {
-    uint32_t nb = std::min(c->batch_cap, n_pods);
-    const size_t rows = std::max<uint32_t>(64u, c->rows_dev);
-    const uint32_t cls_sets = 2u * (c->n_terms + 1u);
-    if ((size_t)std::min(nb, cls_sets) * rows > kNamFBudget)
-        nb = std::max<uint32_t>(256u, (uint32_t)std::min<size_t>(nb, kNamFBudget / rows));
-    return std::max(1u, nb);
+// MS_PLUGINS_NU_NN_NAM: a call's plan (ms_nam_layout.h): pods per chunk, the ONE
+// layout every chunk of the call is carved with, the node-shard inputs behind
+// it, and the allocation. A short last chunk keeps the plan's layout: one of
+// its own pod count can have more row segments and need more scratch than the
+// context holds (tests/cpp/test_nam_layout.cpp, tests/test_gpu_chunks.py).
+NamPlan nam_plan_for(const ms_ctx *c, uint32_t n_pods) {
+    return nam_plan(c->batch_cap, c->rows_dev, c->n_terms, n_pods);
 }
 
-NamLayout nam_layout_for(const ms_ctx *c, uint32_t nb) {
-    return nam_layout(c->rows_dev, std::max(1u, std::min(nb, 2u * (c->n_terms + 1u))));
-}
-
-// Scratch for chunks of nb pods (NamLayout), plus one record (the later shards'
-// table) and one byte (an earlier shard has a non-zero node) per pod. Every NAM
-// call runs on the context stream or chains back into it, so one scratch serves
-// them in order.
-int ensure_nam(ms_ctx *c, uint32_t nb) {
-    const size_t need = nam_scratch_bytes(nam_layout_for(c, nb), nb, c->n_terms) + (size_t)nb * (MS_NAM_SEG_BYTES + 1) + 512;
+// Scratch for the plan: its layout's arrays, plus one record (the later shards'
+// table) and one byte (an earlier shard has a non-zero node) per pod of a
+// chunk. Every NAM call runs on the context stream or chains back into it, so
+// one scratch serves them in order.
+int ensure_nam(ms_ctx *c, const NamPlan &plan) {
+    const size_t need = plan.alloc;
     if (need <= c->nam_bytes) return MS_OK;
     // (growing: a NodeAffinity call on a caller stream may still read the tables; as ensure_tt)
     if (c->d_nam) MS_HIP(c, hipDeviceSynchronize());
@@ -502,24 +493,19 @@ int ensure_nam(ms_ctx *c, uint32_t nb) {
     c->nam_bytes = need;
     return MS_OK;
 }
-// The per-pod shard inputs (after: nb records, m_in: nb bytes) past the layout's scratch.
-char *nam_after(ms_ctx *c, uint32_t nb) {
-    const size_t o = (nam_scratch_bytes(nam_layout_for(c, nb), nb, c->n_terms) + 255u) & ~size_t(255);
-    return static_cast<char *>(c->d_nam) + o;
-}
 
-// This shard's packed keys of nb pods into keys (scratch sized for the chunk):
-// per class its rows' normalised scores under the later segments' and (after /
-// m_in, node shards) the later shards' rescales, then per pod the best key.
-int nam_keys_locked(ms_ctx *c, uint32_t nb, const ms_pod_rec *d_pods, const void *after, const uint8_t *m_in,
-                    unsigned long long *keys, hipStream_t s) {
+// This shard's packed keys of a chunk of nb pods into keys, carved with the
+// call's layout L (the one ensure_nam sized the scratch for): per class its
+// rows' normalised scores under the later segments' and (after / m_in, node
+// shards) the later shards' rescales, then per pod the best key.
+int nam_keys_locked(ms_ctx *c, const NamLayout &L, uint32_t nb, const ms_pod_rec *d_pods, const void *after,
+                    const uint8_t *m_in, unsigned long long *keys, hipStream_t s) {
     if (c->rows_dev == 0) {
         MS_HIP(c, launch_fill_keys(keys, nb, 0ull, s));
         return MS_OK;
     }
     MS_HIP(c, launch_nam_keys(c->t, c->rows_dev, d_pods, nb, c->d_terms, c->n_terms, seed32_of(c->cfg.seed), c->w_nn,
-                              c->w_na, after, m_in, c->present_dev ? 1u : 0u, nam_layout_for(c, nb), c->d_nam, keys,
-                              s));
+                              c->w_na, after, m_in, c->present_dev ? 1u : 0u, L, c->d_nam, keys, s));
     return MS_OK;
 }
 
@@ -527,12 +513,13 @@ int nam_keys_locked(ms_ctx *c, uint32_t nb, const ms_pod_rec *d_pods, const void
 // winner's NodeInfo.AddPod (stateless: no later pod reads it).
 int nam_cycle_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_result *d_res, int commit,
                      hipStream_t s) {
-    const uint32_t B = nam_chunk(c, n_pods);
-    int rc = ensure_nam(c, B);
+    const NamPlan plan = nam_plan_for(c, n_pods);
+    const uint32_t B = plan.chunk;
+    int rc = ensure_nam(c, plan);
     if (rc) return rc;
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
-        rc = nam_keys_locked(c, nb, d_pods + s0, nullptr, nullptr, c->d_keys, s);
+        rc = nam_keys_locked(c, plan.L, nb, d_pods + s0, nullptr, nullptr, c->d_keys, s);
         if (rc) return rc;
         MS_HIP(c, launch_decode(d_pods + s0, nb, c->d_keys, nullptr, c->present_dev, d_res + s0, s));
         if (commit) MS_HIP(c, launch_apply_binds(c->t, d_pods + s0, nb, d_res + s0, s));
@@ -1611,8 +1598,9 @@ int ms_nam_segment_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev
     hipStream_t s = pick_stream(c, stream);
     rc = order_after_ctx_stream(c, s);
     if (rc) return rc;
-    const uint32_t B = nam_chunk(c, n_pods);
-    rc = ensure_nam(c, B);
+    const NamPlan plan = nam_plan_for(c, n_pods);
+    const uint32_t B = plan.chunk;
+    rc = ensure_nam(c, plan);
     if (rc) return rc;
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
@@ -1622,7 +1610,7 @@ int ms_nam_segment_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev
             continue;
         }
         MS_HIP(c, launch_nam_segment(c->t, c->rows_dev, pods_dev + s0, nb, c->d_terms, c->n_terms,
-                                     nam_layout_for(c, nb), c->d_nam, out, s));
+                                     plan.L, c->d_nam, out, s));
     }
     return chain_back(c, s);
 }
@@ -1642,17 +1630,19 @@ int ms_nam_keys_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, u
     hipStream_t s = pick_stream(c, stream);
     rc = order_after_ctx_stream(c, s);
     if (rc) return rc;
-    const uint32_t B = nam_chunk(c, n_pods);
-    rc = ensure_nam(c, B);
+    const NamPlan plan = nam_plan_for(c, n_pods);
+    const uint32_t B = plan.chunk;
+    rc = ensure_nam(c, plan);
     if (rc) return rc;
-    char *after = nam_after(c, B);
-    uint8_t *m_in = reinterpret_cast<uint8_t *>(after + (size_t)B * MS_NAM_SEG_BYTES);
+    // the per-pod shard inputs (B records, B bytes) behind the plan layout's scratch
+    char *after = static_cast<char *>(c->d_nam) + plan.after;
+    uint8_t *m_in = reinterpret_cast<uint8_t *>(static_cast<char *>(c->d_nam) + plan.m_in);
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
         // the later shards' tables composed, and whether an earlier shard has a non-zero node
         MS_HIP(c, launch_nam_compose(static_cast<const char *>(segs_all_dev) + (size_t)s0 * MS_NAM_SEG_BYTES, n_pods,
                                      n_shards, nb, (int32_t)shard_index, after, m_in, s));
-        rc = nam_keys_locked(c, nb, pods_dev + s0, after, m_in, keys_dev + s0, s);
+        rc = nam_keys_locked(c, plan.L, nb, pods_dev + s0, after, m_in, keys_dev + s0, s);
         if (rc) return rc;
     }
     return chain_back(c, s);

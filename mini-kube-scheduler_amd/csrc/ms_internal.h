@@ -169,13 +169,10 @@ struct NamTab {
     uint8_t l[256];
     uint16_t wsum[16];
 };
-// Row segments and scratch shape of one call's per-class passes (cls_max = the
-// most classes a chunk can hold: min(pods, 2 (n_sets + 1))).
-struct NamLayout {
-    uint32_t segs = 1, seg_rows = 64, fpitch = 64, cls_max = 1;
-};
-NamLayout nam_layout(uint32_t n_rows, uint32_t cls_max);
-size_t nam_scratch_bytes(const NamLayout &L, uint32_t n_pods, uint32_t n_sets);
+// NamLayout (row segments and scratch shape), the carve offsets and a call's
+// NamPlan: ms_nam_layout.h (host-only arithmetic). Every chunk of a call is
+// launched with the call's plan layout L, never one of its own pod count.
+struct NamLayout;
 // Node shards, step 1: per pod this context's composed rescale record (out:
 // MS_NAM_SEG_BYTES per pod), computed per class.
 hipError_t launch_nam_segment(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,

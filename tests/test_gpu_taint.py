@@ -43,9 +43,9 @@ def _oracle(oracle, nr, pr, seed, dead=(), literal=False):
     return oracle.schedule_tt(nr, pr, literal=literal, seed=seed)
 
 
-def _engine(nr, seed, lo=0, hi=None, dead=()):
+def _engine(nr, seed, lo=0, hi=None, dead=(), max_batch=1 << 16):
     hi = len(nr) if hi is None else hi
-    e = _lib.Engine(max_nodes=max(1, hi - lo), plugin_set=TT, node_base=lo, seed=seed)
+    e = _lib.Engine(max_nodes=max(1, hi - lo), plugin_set=TT, node_base=lo, seed=seed, max_batch=max_batch)
     e.upsert(np.arange(lo, hi), nr[lo:hi])
     gone = np.asarray([d for d in dead if lo <= d < hi], dtype=np.uint32)
     if len(gone):

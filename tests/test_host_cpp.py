@@ -134,3 +134,21 @@ def test_copy_pool_tsan(tmp_path):
                     "-I", os.path.join(PKG, "csrc"), src, "-o", exe], check=True)
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1")
     assert "0 failed" in _run([exe], env=env)
+
+
+def test_nam_layout_plan_asan(tmp_path):
+    # the NodeAffinity scratch plan (csrc/ms_nam_layout.h, the copy ms_affinity.hip and ms_capi.cpp
+    # use): every chunk of a call, the short last one included, fits the call's allocation; and the
+    # shapes of tests/test_gpu_chunks.py sit where the rule before it (a layout per chunk) overran
+    exe = str(tmp_path / "test_nam_layout")
+    src = os.path.join(ROOT, "tests", "cpp", "test_nam_layout.cpp")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+                    "-I", os.path.join(PKG, "csrc"), src, "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = _run([exe], env=env)
+    print(out)
+    lines = out.splitlines()
+    assert lines[-1] == "0 failed", out
+    assert int(lines[0].split()[3]) > 30_000_000, out  # "grid points checked: N"
+    shapes = [l for l in lines if l.startswith("gpu shape")]
+    assert len(shapes) == 2 and all("overrun" in l for l in shapes), out
