@@ -23,6 +23,13 @@
 
 using namespace msgpu;
 
+// What must happen in order before the members release themselves (ms_ctx.h).
+ms_ctx::~ms_ctx() {
+    (void)hipSetDevice(cfg.device);
+    comm_free(this);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+}
 
 namespace msgpu {
 
@@ -43,59 +50,17 @@ int fail(ms_ctx *c, int code, const std::string &msg) {
 
 constexpr int kSeqBufs = 3;         // sequential-engine batch buffer sets (pipeline depth <= 3)
 
-void free_all(ms_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->cfg.device);
-    comm_free(c);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->d_table) {  // the columns live in it
-        (void)hipFree(c->d_table);
-        c->d_table = nullptr;
-        c->t.flags = c->t.digit = c->t.zone = c->t.label2 = nullptr;
-        c->t.taints = nullptr;
-        c->t.allowed_pods = c->t.pod_count = nullptr;
-        c->t.alloc_cpu = c->t.alloc_mem = c->t.req_cpu = c->t.req_mem = c->t.nz_cpu = c->t.nz_mem = nullptr;
-    }
-    void *dev[] = {c->t.planes, c->d_terms, c->d_nam,
-                   c->d_pods, c->d_res, c->d_keys, c->d_flags, c->d_deltas, c->d_one,
-                   c->d_tile_keys, c->d_tile_flags, c->d_spec, c->d_spec_flags, c->d_top4, c->d_top4_rec, c->d_prev, c->d_prev_rec, c->d_overflow,
-                   c->d_podc, c->d_resc,
-                   c->d_merged, c->d_merged_flags, c->d_drow, c->d_top_ext, c->d_tt,
-                   c->d_merge_tags};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (c->h_podz) (void)hipHostFree(c->h_podz);
-    if (c->h_resz) (void)hipHostFree(c->h_resz);
-    if (c->h_pods) (void)hipHostFree(c->h_pods);
-    if (c->h_res) (void)hipHostFree(c->h_res);
-    if (c->h_deltas) (void)hipHostFree(c->h_deltas);
-    if (c->ev_order) (void)hipEventDestroy(c->ev_order);
-    if (c->ev_back) (void)hipEventDestroy(c->ev_back);
-    if (c->ev_tt) (void)hipEventDestroy(c->ev_tt);
-    if (c->copy_stream) {
-        (void)hipStreamSynchronize(c->copy_stream);
-        (void)hipStreamDestroy(c->copy_stream);
-    }
-    // (the zero-copy path creates ev_cyc without a copy stream)
-    for (int i = 0; i < 4; ++i) {
-        if (c->ev_copy[i]) (void)hipEventDestroy(c->ev_copy[i]);
-        if (c->ev_cyc[i]) (void)hipEventDestroy(c->ev_cyc[i]);
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-}
+// Every grow routine below keeps its capacity at zero while its group of
+// buffers is not whole, so a failed growth is retried by the next call.
 
+// Delta staging for n records. No synchronise of its own: the runtime's free of
+// the old blocks waits for the work that used them (flush_locked's comes after).
 int ensure_delta_cap(ms_ctx *c, uint32_t n) {
     if (n <= c->delta_cap) return MS_OK;
     uint32_t cap = std::max<uint32_t>(n, std::max<uint32_t>(1024, c->delta_cap * 2));
-    if (c->h_deltas) (void)hipHostFree(c->h_deltas);
-    if (c->d_deltas) (void)hipFree(c->d_deltas);
-    c->h_deltas = nullptr;
-    c->d_deltas = nullptr;
     c->delta_cap = 0;
-    if (hipHostMalloc((void **)&c->h_deltas, sizeof(NodeDelta) * cap) != hipSuccess)
-        return fail(c, MS_E_OOM, "pinned delta staging");
-    if (hipMalloc((void **)&c->d_deltas, sizeof(NodeDelta) * cap) != hipSuccess)
-        return fail(c, MS_E_OOM, "device delta staging");
+    if (!c->h_deltas.alloc(cap)) return fail(c, MS_E_OOM, "pinned delta staging");
+    if (!c->d_deltas.alloc(cap)) return fail(c, MS_E_OOM, "device delta staging");
     c->delta_cap = cap;
     return MS_OK;
 }
@@ -146,7 +111,7 @@ int order_after_ctx_stream(ms_ctx *c, hipStream_t s) {
     if (s == c->stream) return MS_OK;
     if (s == c->ordered_stream && c->ordered_seq == c->ctx_seq && c->ordered_fence == c->fence_seq)
         return MS_OK;  // nothing new on the ctx stream
-    if (!c->ev_order) MS_HIP(c, hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming));
+    MS_HIP(c, made(c->ev_order.ensure()));
     hipError_t e = hipEventRecord(c->ev_order, c->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(s, c->ev_order, 0);
     if (e != hipSuccess) return fail(c, MS_E_HIP, std::string("stream ordering: ") + hipGetErrorString(e));
@@ -165,7 +130,7 @@ int order_after_ctx_stream(ms_ctx *c, hipStream_t s) {
 // (by that launch's own dispatch).
 int chain_back(ms_ctx *c, hipStream_t s, bool recorded) {
     if (s == c->stream) return MS_OK;
-    if (!c->ev_back) MS_HIP(c, hipEventCreateWithFlags(&c->ev_back, hipEventDisableTiming));
+    MS_HIP(c, made(c->ev_back.ensure()));
     hipError_t e = recorded ? hipSuccess : hipEventRecord(c->ev_back, s);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_back, 0);
     if (e != hipSuccess) return fail(c, MS_E_HIP, std::string("stream ordering: ") + hipGetErrorString(e));
@@ -183,35 +148,15 @@ int chain_back(ms_ctx *c, hipStream_t s, bool recorded) {
 int ensure_tiles(ms_ctx *c, uint32_t n_tiles) {
     if (n_tiles <= c->tile_cap) return MS_OK;
     MS_HIP(c, hipDeviceSynchronize());  // no batch still reads the old buffers
-    void *old[] = {c->d_tile_keys, c->d_tile_flags, c->d_spec, c->d_spec_flags, c->d_top4, c->d_top4_rec, c->d_prev,
-                   c->d_prev_rec, c->d_drow, c->d_top_ext, c->d_merge_tags};
-    for (void *q : old)
-        if (q) (void)hipFree(q);
-    c->d_tile_keys = nullptr;
-    c->d_tile_flags = nullptr;
-    c->d_spec = nullptr;
-    c->d_spec_flags = nullptr;
-    c->d_top4 = nullptr;
-    c->d_top4_rec = nullptr;
-    c->d_prev = nullptr;
-    c->d_prev_rec = nullptr;
-    c->d_drow = nullptr;
-    c->d_top_ext = nullptr;
-    c->d_merge_tags = nullptr;
     c->tile_cap = 0;
     // (ms_seq_candidates_device uses the same buffers for up to kSeqBufs * B pods)
     const size_t B = seq_batch_limit(), NB = kSeqBufs * B, n = NB * n_tiles;
-    if (hipMalloc((void **)&c->d_tile_keys, n * seq_topk() * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&c->d_tile_flags, n * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&c->d_spec, NB * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&c->d_spec_flags, NB * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&c->d_top4, NB * seq_topk() * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&c->d_top4_rec, NB * seq_topk() * seq_rec_fields() * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void **)&c->d_prev, 2 * (2 + seq_prev_cap()) * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&c->d_prev_rec, 2 * seq_prev_cap() * seq_rec_fields() * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void **)&c->d_drow, (size_t)n_tiles * kFullWaveTile * sizeof(DRow)) != hipSuccess ||
-        hipMalloc((void **)&c->d_top_ext, NB * seq_topk() * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&c->d_merge_tags, NB * sizeof(uint32_t)) != hipSuccess)
+    if (!c->d_tile_keys.alloc(n * seq_topk()) || !c->d_tile_flags.alloc(n) || !c->d_spec.alloc(NB) ||
+        !c->d_spec_flags.alloc(NB) || !c->d_top4.alloc(NB * seq_topk()) ||
+        !c->d_top4_rec.alloc(NB * seq_topk() * seq_rec_fields()) || !c->d_prev.alloc(2 * (2 + seq_prev_cap())) ||
+        !c->d_prev_rec.alloc(2 * seq_prev_cap() * seq_rec_fields()) ||
+        !c->d_drow.alloc((size_t)n_tiles * kFullWaveTile) || !c->d_top_ext.alloc(NB * seq_topk()) ||
+        !c->d_merge_tags.alloc(NB))
         return fail(c, MS_E_OOM, "sequential-engine scratch");
     MS_HIP(c, hipMemsetAsync(c->d_merge_tags, 0, NB * sizeof(uint32_t), c->stream));
     MS_HIP(c, hipMemsetAsync(c->d_spec, 0, NB * sizeof(unsigned long long), c->stream));
@@ -357,8 +302,7 @@ int run_sequential(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resu
 #if defined(MS_VSTAMPS) || defined(MS_TIMELINE_ONLY)
             // diagnostic builds: timeline of steps 0 .. kTimelineSteps - 1 (MS_TIMELINE=<file>)
             static const bool want_tl = getenv("MS_TIMELINE") != nullptr;
-            if (want_tl && !c->d_tl &&
-                hipMalloc((void **)&c->d_tl, (size_t)kTimelineSteps * kTimelineWgs * 8 * 8) == hipSuccess)
+            if (want_tl && !c->d_tl && c->d_tl.alloc((size_t)kTimelineSteps * kTimelineWgs * 8))
                 MS_HIP(c, hipMemsetAsync(c->d_tl, 0, (size_t)kTimelineSteps * kTimelineWgs * 8 * 8, s));
 #endif
             mio.tl = c->d_tl;
@@ -392,25 +336,13 @@ int run_sequential(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resu
 // call, or the queue-order loop, equal one batched sweep.
 bool plugins_stateless(const ms_ctx *c) { return c->cfg.plugin_set != MS_PLUGINS_NU_NRF_NN_LA; }
 
-// Pod / result staging for at least n pods (grown on demand; hipFree
-// synchronises the device, so no in-flight call still uses the old buffers).
+// Pod / result staging for at least n pods (grown on demand). No synchronise
+// of its own: the runtime's free of the old device blocks waits for the
+// device, so no in-flight call still uses them.
 int ensure_stage(ms_ctx *c, uint32_t n) {
     if (n <= c->stage_cap) return MS_OK;
-    void *dev[] = {c->d_pods, c->d_res};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (c->h_pods) (void)hipHostFree(c->h_pods);
-    if (c->h_res) (void)hipHostFree(c->h_res);
-    c->d_pods = nullptr;
-    c->d_res = nullptr;
-    c->h_pods = nullptr;
-    c->h_res = nullptr;
     c->stage_cap = 0;
-    if (hipHostMalloc((void **)&c->h_pods, (size_t)n * sizeof(ms_pod_rec)) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_res, (size_t)n * sizeof(ms_result)) != hipSuccess ||
-        hipMalloc((void **)&c->d_pods, (size_t)n * sizeof(ms_pod_rec)) != hipSuccess ||
-        hipMalloc((void **)&c->d_res, (size_t)n * sizeof(ms_result)) != hipSuccess)
-        return fail(c, MS_E_OOM, "pod staging");
+    if (!c->d_pods.alloc(n) || !c->d_res.alloc(n)) return fail(c, MS_E_OOM, "pod staging");
     c->stage_cap = n;
     return MS_OK;
 }
@@ -421,10 +353,8 @@ int ensure_tt(ms_ctx *c, size_t need) {
     // (growing: the previous scratch may still be read by work on the sweep,
     // collective or decode streams of a node-sharded cycle)
     if (c->d_tt) MS_HIP(c, hipDeviceSynchronize());
-    if (c->d_tt) (void)hipFree(c->d_tt);
-    c->d_tt = nullptr;
     c->tt_bytes = 0;
-    if (hipMalloc(&c->d_tt, need) != hipSuccess) return fail(c, MS_E_OOM, "TaintToleration scratch");
+    if (!c->d_tt.alloc(need)) return fail(c, MS_E_OOM, "TaintToleration scratch");
     c->tt_bytes = need;
     return MS_OK;
 }
@@ -442,7 +372,7 @@ int tt_cycle_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, void *
     int rc = ensure_tt(c, two_pass ? tt2_scratch_bytes(c->rows_dev, cap)
                                    : (size_t)segs * cap * MS_TT_SUMMARY_BYTES);
     if (rc) return rc;
-    if (!c->ev_tt) MS_HIP(c, hipEventCreateWithFlags(&c->ev_tt, hipEventDisableTiming));
+    MS_HIP(c, made(c->ev_tt.ensure()));
     // the previous cycle's sweep/combine on another stream still owns d_tt
     if (c->tt_stream && c->tt_stream != s) MS_HIP(c, hipStreamWaitEvent(s, c->ev_tt, 0));
     const uint32_t seed32 = seed32_of(c->cfg.seed);
@@ -486,10 +416,8 @@ int ensure_nam(ms_ctx *c, const NamPlan &plan) {
     if (need <= c->nam_bytes) return MS_OK;
     // (growing: a NodeAffinity call on a caller stream may still read the tables; as ensure_tt)
     if (c->d_nam) MS_HIP(c, hipDeviceSynchronize());
-    if (c->d_nam) (void)hipFree(c->d_nam);
-    c->d_nam = nullptr;
     c->nam_bytes = 0;
-    if (hipMalloc(&c->d_nam, need) != hipSuccess) return fail(c, MS_E_OOM, "NodeAffinity scratch");
+    if (!c->d_nam.alloc(need)) return fail(c, MS_E_OOM, "NodeAffinity scratch");
     c->nam_bytes = need;
     return MS_OK;
 }
@@ -627,8 +555,8 @@ uint32_t e2e_chunks(uint32_t n) { return std::max(1u, std::min(kE2eChunks, n / k
 // context switches paths); copies: also the copy-stream events.
 int ensure_chunk_events(ms_ctx *c, bool copies) {
     for (int i = 0; i < 4; ++i) {
-        if (!c->ev_cyc[i]) MS_HIP(c, hipEventCreateWithFlags(&c->ev_cyc[i], hipEventDisableTiming));
-        if (copies && !c->ev_copy[i]) MS_HIP(c, hipEventCreateWithFlags(&c->ev_copy[i], hipEventDisableTiming));
+        MS_HIP(c, made(c->ev_cyc[i].ensure()));
+        if (copies) MS_HIP(c, made(c->ev_copy[i].ensure()));
     }
     return MS_OK;
 }
@@ -636,7 +564,7 @@ int ensure_chunk_events(ms_ctx *c, bool copies) {
 int schedule_chunked(ms_ctx *c, const ms_pod_rec *pods, uint32_t n, ms_result *out, uint32_t parts, CallClock &ck) {
     const hipStream_t s = c->stream;
     if (!c->copy_stream) {
-        MS_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+        MS_HIP(c, made(c->copy_stream.ensure(hipStreamNonBlocking)));
         ck.lap(MS_PH_ALLOC);
     }
     int erc = ensure_chunk_events(c, true);
@@ -677,18 +605,14 @@ int schedule_chunked(ms_ctx *c, const ms_pod_rec *pods, uint32_t n, ms_result *o
 }
 
 // Pinned coherent staging of compact records (the compact cycle's kernel reads
-// the pods from and writes the results to it over PCIe), grown to n.
+// the pods from and writes the results to it over PCIe), grown to n. As
+// ensure_delta_cap: the runtime's free waits (schedule_zc's synchronise comes after).
 int ensure_zc(ms_ctx *c, uint32_t n) {
     if (n <= c->z_cap) return MS_OK;
-    if (c->h_podz) (void)hipHostFree(c->h_podz);
-    if (c->h_resz) (void)hipHostFree(c->h_resz);
-    c->h_podz = nullptr;
-    c->h_resz = nullptr;
     c->z_cap = 0;
     // coherent (fine-grained): the kernel's reads see this call's host copy and
     // its writes reach host memory with no cache maintenance between calls
-    if (hipHostMalloc((void **)&c->h_podz, sizeof(ms_pod_compact) * n, hipHostMallocCoherent) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_resz, sizeof(ms_result_compact) * n, hipHostMallocCoherent) != hipSuccess)
+    if (!c->h_podz.alloc(n, hipHostMallocCoherent) || !c->h_resz.alloc(n, hipHostMallocCoherent))
         return fail(c, MS_E_OOM, "compact pinned staging");
     c->z_cap = n;
     return MS_OK;
@@ -867,13 +791,11 @@ int ms_create(const ms_config *cfg, ms_ctx **out) {
 
     auto bail = [&](int code, const char *what) {
         std::string m = std::string("ms_create: ") + what;
-        free_all(c);
         delete c;
         return fail(nullptr, code, m);
     };
     if (hipSetDevice(cfg->device) != hipSuccess) return bail(MS_E_HIP, "hipSetDevice");
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(MS_E_HIP, "hipStreamCreate");
+    if (!c->stream.ensure(hipStreamNonBlocking)) return bail(MS_E_HIP, "stream creation");
     const size_t n = cfg->max_nodes;
     NodeTable &t = c->t;
     t.cap = cfg->max_nodes;
@@ -894,19 +816,17 @@ int ms_create(const ms_config *cfg, ms_ctx **out) {
         total += (bytes[i] + 255) & ~(size_t)255;
     }
     total = (total + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
-    bool ok = hipMalloc(&c->d_table, total) == hipSuccess;
+    bool ok = c->d_table.alloc(total);
     if (ok)
         for (size_t i = 0; i < sizeof(bytes) / sizeof(bytes[0]); ++i)
-            *cols[i] = static_cast<char *>(c->d_table) + off[i];
+            *cols[i] = static_cast<char *>(c->d_table.get()) + off[i];
     t.gcap = (uint32_t)((n + kGroupRows - 1) / kGroupRows);
-    ok = ok && hipMalloc((void **)&t.planes, sizeof(uint32_t) * kPlanes * t.gcap) == hipSuccess;
+    ok = ok && c->d_planes.alloc((size_t)kPlanes * t.gcap);
     if (!ok) return bail(MS_E_OOM, "node table allocation");
+    t.planes = c->d_planes;
     const size_t b = c->batch_cap;
-    ok = ensure_stage(c, c->batch_cap) == MS_OK &&
-         hipMalloc((void **)&c->d_keys, b * sizeof(unsigned long long)) == hipSuccess &&
-         hipMalloc((void **)&c->d_flags, b * sizeof(uint32_t)) == hipSuccess &&
-         hipMalloc((void **)&c->d_one, sizeof(ms_pod_rec)) == hipSuccess &&
-         hipMalloc((void **)&c->d_overflow, kStatsBytes) == hipSuccess;
+    ok = ensure_stage(c, c->batch_cap) == MS_OK && c->d_keys.alloc(b) && c->d_flags.alloc(b) && c->d_one.alloc(1) &&
+         c->d_overflow.alloc(kStatsBytes / sizeof(uint32_t));
     if (!ok) return bail(MS_E_OOM, "staging allocation");
     if (launch_init_table(t, c->stream) != hipSuccess || launch_build_planes(t, nullptr, 0, c->stream) != hipSuccess)
         return bail(MS_E_HIP, "table init launch");
@@ -954,13 +874,9 @@ int ms_destroy(ms_ctx *c) {
                     std::fclose(f);
                 }
             }
-            (void)hipFree(c->d_tl);
-            c->d_tl = nullptr;
         }
     }
 #endif
-    if (c->d_tl) (void)hipFree(c->d_tl);
-    free_all(c);
     delete c;
     return MS_OK;
 }
@@ -1059,12 +975,11 @@ int ms_nodes_read(ms_ctx *c, uint32_t first, uint32_t n, ms_node_rec *out) {
     MS_HIP(c, hipSetDevice(c->cfg.device));
     int rc = flush_locked(c);
     if (rc) return rc;
-    ms_node_rec *d = nullptr;
-    MS_HIP(c, hipMalloc((void **)&d, sizeof(ms_node_rec) * n));
+    DevBuf<ms_node_rec> d;  // (released on return, after the synchronise below)
+    MS_HIP(c, made(d.alloc(n)));
     hipError_t e = launch_read_rows(c->t, first - c->cfg.node_base, n, d, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(ms_node_rec) * n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(c, MS_E_HIP, std::string("ms_nodes_read: ") + hipGetErrorString(e));
     return MS_OK;
 }
@@ -1100,7 +1015,9 @@ int ms_schedule_batch(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods, int32_
     // returns, so no caller (cgo) pointer outlives it.
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
-        MS_HIP(c, hipStreamSynchronize(s));  // h_pods / h_res free to reuse
+        // (the stream is already idle after the previous chunk's synchronise; kept
+        // because it delimits the MS_PH_WAIT phase of the call profile)
+        MS_HIP(c, hipStreamSynchronize(s));
         ck.lap(MS_PH_WAIT);
         const bool seq_full = (mode == MS_MODE_SEQUENTIAL && c->cfg.plugin_set == MS_PLUGINS_NU_NRF_NN_LA);
         const uint32_t parts = plugins_stateless(c) ? e2e_chunks(nb) : 1u;
@@ -1150,15 +1067,9 @@ int ms_schedule_batch_compact(ms_ctx *c, uint32_t n, const ms_pod_compact *pods,
         return schedule_zc(c, pods, n, out, ck);
     rc = c->comm ? comm_stage(c, n) : ensure_stage(c, n);
     if (rc) return rc;
-    if (n > c->compact_cap) {
-        if (c->d_podc) (void)hipFree(c->d_podc);
-        if (c->d_resc) (void)hipFree(c->d_resc);
-        c->d_podc = nullptr;
-        c->d_resc = nullptr;
+    if (n > c->compact_cap) {  // (as ensure_stage: the runtime's free waits for the device)
         c->compact_cap = 0;
-        if (hipMalloc((void **)&c->d_podc, sizeof(ms_pod_compact) * n) != hipSuccess ||
-            hipMalloc((void **)&c->d_resc, sizeof(ms_result_compact) * n) != hipSuccess)
-            return fail(c, MS_E_OOM, "compact staging");
+        if (!c->d_podc.alloc(n) || !c->d_resc.alloc(n)) return fail(c, MS_E_OOM, "compact staging");
         c->compact_cap = n;
     }
     ck.lap(MS_PH_ALLOC);
@@ -1222,7 +1133,7 @@ int ms_sweep_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, uint
     // on a caller stream the chain-back event is recorded by the sweep's own dispatch
     hipEvent_t back = nullptr;
     if (s != c->stream) {
-        if (!c->ev_back) MS_HIP(c, hipEventCreateWithFlags(&c->ev_back, hipEventDisableTiming));
+        MS_HIP(c, made(c->ev_back.ensure()));
         back = c->ev_back;
     }
     rc = sweep_locked(c, n_pods, pods_dev, reinterpret_cast<unsigned long long *>(keys_dev), flags_dev, s, back);
@@ -1246,7 +1157,7 @@ int ms_select_batch_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_de
     // on a caller stream the chain-back event is recorded by the cycle's own dispatch
     hipEvent_t back = nullptr;
     if (s != c->stream) {
-        if (!c->ev_back) MS_HIP(c, hipEventCreateWithFlags(&c->ev_back, hipEventDisableTiming));
+        MS_HIP(c, made(c->ev_back.ensure()));
         back = c->ev_back;
     }
     rc = select_locked(c, n_pods, pods_dev, results_dev, s, 0, back);
@@ -1369,11 +1280,10 @@ int ms_seq_validate_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_de
     }
     int rc = order_after_ctx_stream(c, s);  // (deltas are not drained here: the candidates' records must stay current)
     if (rc) return rc;
-    if (!c->d_merged) {
-        if (hipMalloc((void **)&c->d_merged, sizeof(ms_seq_cand) * kTopKCands * MS_SEQ_SHARD_BATCH_MAX) != hipSuccess ||
-            hipMalloc((void **)&c->d_merged_flags, sizeof(uint32_t) * MS_SEQ_SHARD_BATCH_MAX) != hipSuccess)
-            return fail(c, MS_E_OOM, "sharded validator scratch");
-    }
+    if (!c->d_merged_flags &&  // (the second of the pair: set only when both are)
+        (!c->d_merged.alloc((size_t)kTopKCands * MS_SEQ_SHARD_BATCH_MAX) ||
+         !c->d_merged_flags.alloc(MS_SEQ_SHARD_BATCH_MAX)))
+        return fail(c, MS_E_OOM, "sharded validator scratch");
     MS_HIP(c, launch_seq_validate_rep(c->t, n_pods, pods_dev, seed32_of(c->cfg.seed), n_shards, cands_all_dev,
                                       flags_all_dev, c->d_merged, c->d_merged_flags, results_dev, n_done_dev, s));
     if (s == c->stream) {
@@ -1425,7 +1335,7 @@ static int tt2_shard_prologue(ms_ctx *c, uint32_t n_pods, const char *who, hipSt
     if (rc) return rc;
     rc = ensure_tt(c, tt2_scratch_bytes(c->rows_dev, std::min(c->batch_cap, n_pods)));
     if (rc) return rc;
-    if (!c->ev_tt) MS_HIP(c, hipEventCreateWithFlags(&c->ev_tt, hipEventDisableTiming));
+    MS_HIP(c, made(c->ev_tt.ensure()));
     if (c->tt_stream && c->tt_stream != s) MS_HIP(c, hipStreamWaitEvent(s, c->ev_tt, 0));
     if (planes) MS_HIP(c, launch_tt2_planes(c->t, c->rows_dev, c->d_tt, s));
     return MS_OK;
@@ -1543,10 +1453,8 @@ static int nam_install(ms_ctx *c, const std::vector<NamTab> &tabs, const char *w
     MS_HIP(c, hipSetDevice(c->cfg.device));
     MS_HIP(c, hipDeviceSynchronize());  // (no cycle still reads the previous table; a configuration call)
     if (n_sets > c->terms_cap) {
-        if (c->d_terms) (void)hipFree(c->d_terms);
-        c->d_terms = nullptr;
-        c->terms_cap = 0;
-        if (hipMalloc(&c->d_terms, (size_t)n_sets * sizeof(NamTab)) != hipSuccess)
+        c->terms_cap = c->n_terms = 0;  // (no table, no sets, should the allocation fail)
+        if (!c->d_terms.alloc((size_t)n_sets * sizeof(NamTab)))
             return fail(c, MS_E_OOM, std::string(who) + ": term table");
         c->terms_cap = n_sets;
     }
@@ -1635,8 +1543,8 @@ int ms_nam_keys_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, u
     rc = ensure_nam(c, plan);
     if (rc) return rc;
     // the per-pod shard inputs (B records, B bytes) behind the plan layout's scratch
-    char *after = static_cast<char *>(c->d_nam) + plan.after;
-    uint8_t *m_in = reinterpret_cast<uint8_t *>(static_cast<char *>(c->d_nam) + plan.m_in);
+    char *after = static_cast<char *>(c->d_nam.get()) + plan.after;
+    uint8_t *m_in = reinterpret_cast<uint8_t *>(static_cast<char *>(c->d_nam.get()) + plan.m_in);
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
         // the later shards' tables composed, and whether an earlier shard has a non-zero node

@@ -75,13 +75,13 @@ static_assert(sizeof(ncclUniqueId) == MS_COMM_ID_BYTES, "ms_comm_id holds an ncc
 
 // One in-flight batch's combine buffers.
 struct ShardSlot {
-    unsigned long long *keys = nullptr;       // G x cap: this shard's maxima, pod order
-    unsigned long long *keys_mine = nullptr;  // cap: the cluster's maxima of this rank's slice
-    uint32_t *flags = nullptr, *flags_mine = nullptr;
+    DevBuf<unsigned long long> keys;       // G x cap: this shard's maxima, pod order
+    DevBuf<unsigned long long> keys_mine;  // cap: the cluster's maxima of this rank's slice
+    DevBuf<uint32_t> flags, flags_mine;
     // MS_PLUGINS_NU_TT_NN, the two-pass form: this shard's census (G x cap records, pod
     // order), every shard's after the all-gather (G x G x cap, shard-major,
     // stride = the batch), and the slice's plans for the final pass
-    void *cen_mine = nullptr, *cen_all = nullptr, *plans = nullptr;
+    DevBuf<void> cen_mine, cen_all, plans;
     uint32_t cap = 0;       // pods per slice the buffers hold
     bool used = false;      // a batch went through this slot
     uint64_t dec_gen = 0;   // the drain that decoded its last batch
@@ -98,12 +98,15 @@ struct Pending {
 struct CommState {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
-    hipStream_t cs = nullptr;  // collective stream
-    hipStream_t ss[2] = {nullptr, nullptr};  // sweep streams, alternating batch by batch
-    hipEvent_t ev_swept[kPipeMax] = {}, ev_comb[kPipeMax] = {};
-    hipEvent_t ev_ag[kPipeMax] = {};  // TaintToleration two-pass: the slot's census all-gather
-    hipEvent_t ev_in = nullptr, ev_ctx = nullptr;  // caller stream -> sweep stream, context stream -> sweep stream
-    hipEvent_t ev_drained = nullptr;               // after the newest drain's decodes (decode stream)
+    // (the streams first: members release in reverse order, so they outlive the
+    // events and buffers used on them)
+    Stream cs;     // collective stream
+    Stream ss[2];  // sweep streams, alternating batch by batch
+    Stream ds;     // decode stream (the drains; callers wait on it in ms_sharded_drain)
+    Event ev_swept[kPipeMax], ev_comb[kPipeMax];
+    Event ev_ag[kPipeMax];  // TaintToleration two-pass: the slot's census all-gather
+    Event ev_in, ev_ctx;    // caller stream -> sweep stream, context stream -> sweep stream
+    Event ev_drained;       // after the newest drain's decodes (decode stream)
     uint64_t drains = 0, cs_drain_seen = 0;        // drains enqueued / the newest the collective stream waited for
     bool two_streams = false;  // MINISCHED_SHARD_STREAMS=2: sweeps alternate over ss[0], ss[1] (A/B)
     bool reads_outstanding = false;                // sweeps since the last fence
@@ -115,16 +118,15 @@ struct CommState {
     uint64_t x_comb_seen = 0;       // x_stream waited for the collectives of submissions < this
     hipStream_t x_stream = nullptr;
     uint32_t depth = 4, group = 4;
-    hipStream_t ds = nullptr;           // decode stream (the drains; callers wait on it in ms_sharded_drain)
-    hipEvent_t ev_ds = nullptr;
+    Event ev_ds;
     // node-sharded exact sequential
     uint32_t seq_w = 0;
-    ms_pod_rec *win_pods = nullptr;
-    ms_result *win_res = nullptr;
-    uint32_t *ctl = nullptr;    // {cursor, live, n_done, pad}
-    uint32_t *h_ctl = nullptr;  // pinned read-back of the cursor
-    ms_seq_cand *cands = nullptr, *cands_all = nullptr, *merged = nullptr;
-    uint32_t *sflags = nullptr, *sflags_all = nullptr, *merged_flags = nullptr;
+    DevBuf<ms_pod_rec> win_pods;
+    DevBuf<ms_result> win_res;
+    DevBuf<uint32_t> ctl;       // {cursor, live, n_done, pad}
+    PinnedBuf<uint32_t> h_ctl;  // pinned read-back of the cursor
+    DevBuf<ms_seq_cand> cands, cands_all, merged;
+    DevBuf<uint32_t> sflags, sflags_all, merged_flags;
     uint64_t seq_windows = 0, seq_rounds = 0;
     // coalesced submits: a NU+NN submission whose sweep waits to share the next one's launch
     struct Stash {
@@ -138,6 +140,21 @@ struct CommState {
     // MINISCHED_HOST_PROF=1: host time of ms_sharded_submit's phases (ns), printed at ms_destroy
     bool host_prof = false;
     uint64_t hp[6] = {0, 0, 0, 0, 0, 0}, hp_calls = 0;
+
+    // In this order: the host profile, every stream and the device idle, the
+    // communicator gone; the members then release themselves.
+    ~CommState() {
+        if (host_prof && hp_calls)
+            std::fprintf(stderr, "MS_HOST_PROF submits=%llu us/submit: order=%.2f sweep=%.2f events=%.2f rccl=%.2f tail=%.2f\n",
+                         (unsigned long long)hp_calls, hp[0] * 1e-3 / hp_calls, hp[1] * 1e-3 / hp_calls,
+                         hp[2] * 1e-3 / hp_calls, hp[3] * 1e-3 / hp_calls, hp[4] * 1e-3 / hp_calls);
+        for (hipStream_t q : ss)
+            if (q) (void)hipStreamSynchronize(q);
+        if (cs) (void)hipStreamSynchronize(cs);
+        if (ds) (void)hipStreamSynchronize(ds);
+        (void)hipDeviceSynchronize();
+        if (comm) (void)CCL(ncclCommDestroy)(comm);
+    }
 };
 
 namespace {
@@ -149,31 +166,22 @@ namespace {
             return fail((c), MS_E_RCCL, std::string(#call) + ": " + CCL(ncclGetErrorString)(r_));      \
     } while (0)
 
-void free_slot(ShardSlot &sl) {
-    void *p[] = {sl.keys, sl.keys_mine, sl.flags, sl.flags_mine, sl.cen_mine, sl.cen_all, sl.plans};
-    for (void *q : p)
-        if (q) (void)hipFree(q);
-    sl = ShardSlot{};
-}
-
-// Buffers of a slot for slices of `per` pods (grown; the slot's previous batch
-// has been drained, and hipFree waits for its decode).
+// Buffers of a slot for slices of `per` pods, rounded up to 1024 (grown; the
+// slot's previous batch has been drained). No synchronise of its own: the
+// runtime's free of the old blocks waits for that batch's decode, so the slot
+// starts over as unused.
 int slot_ensure(ms_ctx *c, ShardSlot &sl, uint32_t per) {
-    if (per <= sl.cap && sl.keys) return MS_OK;
+    if (per <= sl.cap) return MS_OK;
     const size_t G = (size_t)c->comm->world;
     const uint32_t cap = std::max<uint32_t>(1024u, cdiv(per, 1024u) * 1024u);
-    free_slot(sl);
-    if (hipMalloc((void **)&sl.keys, G * cap * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&sl.keys_mine, cap * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&sl.flags, G * cap * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&sl.flags_mine, cap * sizeof(uint32_t)) != hipSuccess ||
+    sl.cap = 0;
+    sl.used = false;
+    sl.dec_gen = 0;
+    if (!sl.keys.alloc(G * cap) || !sl.keys_mine.alloc(cap) || !sl.flags.alloc(G * cap) || !sl.flags_mine.alloc(cap) ||
         (c->cfg.plugin_set == MS_PLUGINS_NU_TT_NN &&
-         (hipMalloc(&sl.cen_mine, G * cap * MS_TT_CENSUS_BYTES) != hipSuccess ||
-          hipMalloc(&sl.cen_all, G * G * cap * MS_TT_CENSUS_BYTES) != hipSuccess ||
-          hipMalloc(&sl.plans, cap * MS_TT_CENSUS_BYTES) != hipSuccess))) {
-        free_slot(sl);
+         (!sl.cen_mine.alloc(G * cap * MS_TT_CENSUS_BYTES) || !sl.cen_all.alloc(G * G * cap * MS_TT_CENSUS_BYTES) ||
+          !sl.plans.alloc((size_t)cap * MS_TT_CENSUS_BYTES))))
         return fail(c, MS_E_OOM, "sharded combine buffers");
-    }
     sl.cap = cap;
     return MS_OK;
 }
@@ -198,7 +206,7 @@ int drain_locked(ms_ctx *c, size_t k) {
             const Pending &p = m.pending[i];
             const ShardSlot &sl = m.slot[p.slot];
             MS_HIP(c, launch_tt2_final_shard(c->t, c->rows_dev, p.pods + p.first, p.count, seed32_of(c->cfg.seed),
-                                             sl.plans, p.count, static_cast<const char *>(sl.cen_all) +
+                                             sl.plans, p.count, static_cast<const char *>(sl.cen_all.get()) +
                                                                     (size_t)p.first * MS_TT_CENSUS_BYTES,
                                              p.n, (uint32_t)m.world, sl.keys_mine, p.results, s));
         }
@@ -265,7 +273,7 @@ int prepare_locked(ms_ctx *c, uint32_t n, hipStream_t s, uint32_t &si, hipStream
     const uint32_t G = (uint32_t)m.world, per = cdiv(n, G);
     si = (uint32_t)(m.submitted % (m.depth + 1));
     const int xi = (int)(m.submitted & 1u);
-    X = m.two_streams ? m.ss[xi] : s;
+    X = m.two_streams ? m.ss[xi].get() : s;
     ShardSlot &sl = m.slot[si];
     int rc = slot_ensure(c, sl, per);
     if (rc) return rc;
@@ -368,7 +376,7 @@ int tt2_sharded_sweep(ms_ctx *c, uint32_t si, uint32_t n, const ms_pod_rec *pods
     const uint32_t seed32 = seed32_of(c->cfg.seed);
     int rc = ensure_tt(c, tt2_scratch_bytes(c->rows_dev, std::max(1u, n)));
     if (rc) return rc;
-    if (!c->ev_tt) MS_HIP(c, hipEventCreateWithFlags(&c->ev_tt, hipEventDisableTiming));
+    MS_HIP(c, made(c->ev_tt.ensure()));
     if (c->tt_stream && c->tt_stream != X) MS_HIP(c, hipStreamWaitEvent(X, c->ev_tt, 0));
     MS_HIP(c, launch_tt2_planes(c->t, c->rows_dev, c->d_tt, X));
     MS_HIP(c, launch_tt2_census_shard(c->t, c->rows_dev, pods, n, seed32, c->d_tt, std::max(1u, n), sl.cen_mine, X));
@@ -450,26 +458,11 @@ int seq_ensure(ms_ctx *c, uint32_t w) {
     CommState &m = *c->comm;
     if (w <= m.seq_w) return MS_OK;
     MS_HIP(c, hipDeviceSynchronize());
-    void *old[] = {m.win_pods, m.win_res, m.ctl, m.cands, m.cands_all, m.merged, m.sflags, m.sflags_all, m.merged_flags};
-    for (void *q : old)
-        if (q) (void)hipFree(q);
-    if (m.h_ctl) (void)hipHostFree(m.h_ctl);
-    m.win_pods = nullptr;
-    m.win_res = nullptr;
-    m.ctl = m.h_ctl = m.sflags = m.sflags_all = m.merged_flags = nullptr;
-    m.cands = m.cands_all = m.merged = nullptr;
     m.seq_w = 0;
     const size_t G = (size_t)m.world, K = kTopKCands;
-    if (hipMalloc((void **)&m.win_pods, w * sizeof(ms_pod_rec)) != hipSuccess ||
-        hipMalloc((void **)&m.win_res, w * sizeof(ms_result)) != hipSuccess ||
-        hipMalloc((void **)&m.ctl, 4 * sizeof(uint32_t)) != hipSuccess ||
-        hipHostMalloc((void **)&m.h_ctl, 4 * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&m.cands, w * K * sizeof(ms_seq_cand)) != hipSuccess ||
-        hipMalloc((void **)&m.cands_all, G * w * K * sizeof(ms_seq_cand)) != hipSuccess ||
-        hipMalloc((void **)&m.merged, w * K * sizeof(ms_seq_cand)) != hipSuccess ||
-        hipMalloc((void **)&m.sflags, w * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&m.sflags_all, G * w * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&m.merged_flags, w * sizeof(uint32_t)) != hipSuccess)
+    if (!m.win_pods.alloc(w) || !m.win_res.alloc(w) || !m.ctl.alloc(4) || !m.h_ctl.alloc(4) || !m.cands.alloc(w * K) ||
+        !m.cands_all.alloc(G * w * K) || !m.merged.alloc(w * K) || !m.sflags.alloc(w) || !m.sflags_all.alloc(G * w) ||
+        !m.merged_flags.alloc(w))
         return fail(c, MS_E_OOM, "sharded sequential buffers");
     m.seq_w = w;
     return MS_OK;
@@ -562,38 +555,7 @@ int comm_fence_reads(ms_ctx *c, hipStream_t writer) {
 }
 
 void comm_free(ms_ctx *c) {
-    CommState *m = c->comm;
-    if (!m) return;
-    if (m->host_prof && m->hp_calls)
-        std::fprintf(stderr, "MS_HOST_PROF submits=%llu us/submit: order=%.2f sweep=%.2f events=%.2f rccl=%.2f tail=%.2f\n",
-                     (unsigned long long)m->hp_calls, m->hp[0] * 1e-3 / m->hp_calls, m->hp[1] * 1e-3 / m->hp_calls,
-                     m->hp[2] * 1e-3 / m->hp_calls, m->hp[3] * 1e-3 / m->hp_calls, m->hp[4] * 1e-3 / m->hp_calls);
-    for (hipStream_t q : m->ss)
-        if (q) (void)hipStreamSynchronize(q);
-    if (m->cs) (void)hipStreamSynchronize(m->cs);
-    if (m->ds) (void)hipStreamSynchronize(m->ds);
-    (void)hipDeviceSynchronize();
-    if (m->comm) (void)CCL(ncclCommDestroy)(m->comm);
-    for (uint32_t i = 0; i < kPipeMax; ++i) {
-        free_slot(m->slot[i]);
-        if (m->ev_swept[i]) (void)hipEventDestroy(m->ev_swept[i]);
-        if (m->ev_comb[i]) (void)hipEventDestroy(m->ev_comb[i]);
-        if (m->ev_ag[i]) (void)hipEventDestroy(m->ev_ag[i]);
-    }
-    if (m->ev_drained) (void)hipEventDestroy(m->ev_drained);
-    if (m->ev_in) (void)hipEventDestroy(m->ev_in);
-    if (m->ev_ds) (void)hipEventDestroy(m->ev_ds);
-    if (m->ds) (void)hipStreamDestroy(m->ds);
-    if (m->ev_ctx) (void)hipEventDestroy(m->ev_ctx);
-    for (hipStream_t q : m->ss)
-        if (q) (void)hipStreamDestroy(q);
-    void *dev[] = {m->win_pods, m->win_res, m->ctl, m->cands, m->cands_all, m->merged, m->sflags, m->sflags_all,
-                   m->merged_flags};
-    for (void *q : dev)
-        if (q) (void)hipFree(q);
-    if (m->h_ctl) (void)hipHostFree(m->h_ctl);
-    if (m->cs) (void)hipStreamDestroy(m->cs);
-    delete m;
+    delete c->comm;
     c->comm = nullptr;
 }
 
@@ -659,21 +621,21 @@ int comm_setup(ms_ctx *c, CommState &m, const ms_comm_id *id, int32_t rank, int3
     int lo = 0, hi = 0;
     MS_HIP(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
     const int cprio = hi;
-    MS_HIP(c, hipStreamCreateWithPriority(&m.cs, hipStreamNonBlocking, cprio));
+    MS_HIP(c, made(m.cs.ensure(hipStreamNonBlocking, cprio)));
     // (MINISCHED_SHARD_STREAMS=2 only) two sweep streams at normal priority (at the
     // highest, the collectives fell behind)
     if (m.two_streams)
-        for (hipStream_t &q : m.ss) MS_HIP(c, hipStreamCreateWithPriority(&q, hipStreamNonBlocking, 0));
-    MS_HIP(c, hipStreamCreateWithPriority(&m.ds, hipStreamNonBlocking, cprio));
-    MS_HIP(c, hipEventCreateWithFlags(&m.ev_ds, hipEventDisableTiming));
+        for (Stream &q : m.ss) MS_HIP(c, made(q.ensure(hipStreamNonBlocking, 0)));
+    MS_HIP(c, made(m.ds.ensure(hipStreamNonBlocking, cprio)));
+    MS_HIP(c, made(m.ev_ds.ensure()));
     for (uint32_t i = 0; i < kPipeMax; ++i) {
-        MS_HIP(c, hipEventCreateWithFlags(&m.ev_swept[i], hipEventDisableTiming));
-        MS_HIP(c, hipEventCreateWithFlags(&m.ev_comb[i], hipEventDisableTiming));
-        MS_HIP(c, hipEventCreateWithFlags(&m.ev_ag[i], hipEventDisableTiming));
+        MS_HIP(c, made(m.ev_swept[i].ensure()));
+        MS_HIP(c, made(m.ev_comb[i].ensure()));
+        MS_HIP(c, made(m.ev_ag[i].ensure()));
     }
-    MS_HIP(c, hipEventCreateWithFlags(&m.ev_drained, hipEventDisableTiming));
-    MS_HIP(c, hipEventCreateWithFlags(&m.ev_in, hipEventDisableTiming));
-    MS_HIP(c, hipEventCreateWithFlags(&m.ev_ctx, hipEventDisableTiming));
+    MS_HIP(c, made(m.ev_drained.ensure()));
+    MS_HIP(c, made(m.ev_in.ensure()));
+    MS_HIP(c, made(m.ev_ctx.ensure()));
     ncclUniqueId uid;
     std::memcpy(&uid, id->internal, sizeof(uid));
     const ncclResult_t r = CCL(ncclCommInitRank)(&m.comm, world, uid, rank);

@@ -10,24 +10,91 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ms_copy_pool.h"
 #include "ms_internal.h"
+#include "ms_owned.h"
 
 namespace msgpu {
 struct CommState;
-}
 
+// The release policies of ms_owned.h: the only place that allocates or frees
+// device and pinned memory and creates or destroys events and streams.
+template <class T>  // (buffers count elements of T; a void buffer bytes)
+constexpr size_t kElemBytes = sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
+
+template <class T>
+struct DevMem {
+    using handle = T *;
+    static T *acquire(size_t count) {
+        void *p = nullptr;
+        return hipMalloc(&p, count * kElemBytes<T>) == hipSuccess ? static_cast<T *>(p) : nullptr;
+    }
+    static void release(T *p) { (void)hipFree(p); }
+};
+template <class T>
+struct PinnedMem {
+    using handle = T *;
+    static T *acquire(size_t count, unsigned flags = hipHostMallocDefault) {
+        void *p = nullptr;
+        return hipHostMalloc(&p, count * kElemBytes<T>, flags) == hipSuccess ? static_cast<T *>(p) : nullptr;
+    }
+    static void release(T *p) { (void)hipHostFree(p); }
+};
+struct EventRes {
+    using handle = hipEvent_t;
+    static hipEvent_t acquire() {
+        hipEvent_t e = nullptr;
+        return hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess ? e : nullptr;
+    }
+    static void release(hipEvent_t e) { (void)hipEventDestroy(e); }
+};
+struct StreamRes {
+    using handle = hipStream_t;
+    static hipStream_t acquire(unsigned flags) {
+        hipStream_t s = nullptr;
+        return hipStreamCreateWithFlags(&s, flags) == hipSuccess ? s : nullptr;
+    }
+    static hipStream_t acquire(unsigned flags, int priority) {
+        hipStream_t s = nullptr;
+        return hipStreamCreateWithPriority(&s, flags, priority) == hipSuccess ? s : nullptr;
+    }
+    static void release(hipStream_t s) { (void)hipStreamDestroy(s); }
+};
+template <class T>
+using DevBuf = Owned<DevMem<T>>;
+template <class T>
+using PinnedBuf = Owned<PinnedMem<T>>;
+using Event = Owned<EventRes>;
+using Stream = Owned<StreamRes>;
+
+// For MS_HIP around an owner's alloc / ensure: the runtime's error behind a false.
+inline hipError_t made(bool ok) { return ok ? hipSuccess : hipGetLastError(); }
+}  // namespace msgpu
+
+using msgpu::DevBuf;
 using msgpu::DRow;
+using msgpu::Event;
 using msgpu::NodeDelta;
 using msgpu::NodeTable;
+using msgpu::PinnedBuf;
+using msgpu::Stream;
 
 struct ms_ctx {
     ms_config cfg{};
-    hipStream_t stream = nullptr;
+    // Owners release themselves in reverse declaration order: the two streams
+    // are declared first, so they outlive every event and buffer used on them.
+    Stream stream;
+    // ms_schedule_batch's chunked copies (schedule_chunked): H2D / D2H of host arrays beside the cycle
+    Stream copy_stream;
     int num_cus = 0;
-    NodeTable t{};
+    NodeTable t{};  // raw views: its columns point into d_table, t.planes is d_planes
+    DevBuf<void> d_table;  // the node table's columns, one allocation (ms_create)
+    DevBuf<uint32_t> d_planes;
+    ~ms_ctx();  // device set, communicator freed, both streams drained; then the members (ms_capi.cpp)
+
     // helper threads for the host copies of single-shard host-array calls
     // (ms_copy_pool.h; created on the first large call, joined when the context is deleted)
     std::unique_ptr<msgpu::CopyPool> copy_pool;
@@ -46,66 +113,60 @@ struct ms_ctx {
     // one scheduling caller at a time (minisched.go:28-30 runs one goroutine)
     std::mutex sched_mu;
 
-    // staging (d_pods / d_res / h_pods / h_res hold stage_cap pods; the key and
-    // flag scratch batch_cap; the compact records compact_cap)
+    // staging (d_pods / d_res hold stage_cap pods; the key and flag scratch
+    // batch_cap; the compact records compact_cap)
     uint32_t batch_cap = 0, stage_cap = 0, compact_cap = 0;
-    ms_pod_compact *d_podc = nullptr;
-    ms_result_compact *d_resc = nullptr;
-    ms_pod_rec *h_pods = nullptr;
-    ms_result *h_res = nullptr;
-    ms_pod_rec *d_pods = nullptr;
-    ms_result *d_res = nullptr;
-    unsigned long long *d_keys = nullptr;
-    uint32_t *d_flags = nullptr;  // per-pod filter flags (set 1) / NodeAffinity anchors (set 2)
+    DevBuf<ms_pod_compact> d_podc;
+    DevBuf<ms_result_compact> d_resc;
+    DevBuf<ms_pod_rec> d_pods;
+    DevBuf<ms_result> d_res;
+    DevBuf<unsigned long long> d_keys;
+    DevBuf<uint32_t> d_flags;     // per-pod filter flags (set 1) / NodeAffinity anchors (set 2)
     uint32_t w_nn = 1, w_na = 1;  // score weights (MS_PLUGINS_NU_NN_NA)
-    NodeDelta *h_deltas = nullptr;
-    NodeDelta *d_deltas = nullptr;
+    PinnedBuf<NodeDelta> h_deltas;
+    DevBuf<NodeDelta> d_deltas;
     uint32_t delta_cap = 0;
-    ms_pod_rec *d_one = nullptr;  // commit/uncommit staging
+    DevBuf<ms_pod_rec> d_one;  // commit/uncommit staging
 
     // sequential engine scratch
-    unsigned long long *d_tile_keys = nullptr;
-    uint32_t *d_tile_flags = nullptr;
-    unsigned long long *d_spec = nullptr;  // per-pod speculative winner key (atomicMax target)
-    uint32_t *d_spec_flags = nullptr;      // per-pod flags of tiles with no feasible row (atomicOr target)
-    unsigned long long *d_top4 = nullptr;  // per-pod global speculative top-4 keys
-    int64_t *d_top4_rec = nullptr;         // their batch-start node records (validator layout)
-    unsigned long long *d_top_ext = nullptr;  // ranks 4..7 per pod (the validator's slow pods)
-    uint32_t *d_merge_tags = nullptr;         // per pod of both merge-output sets: the in-step merge's tag
-    void *d_table = nullptr;                  // the node table's columns, one allocation (ms_create)
-    uint32_t merge_tag = 0;                   // last in-step merge tag issued
-    unsigned long long *d_tl = nullptr;       // MS_VSTAMPS: step timeline (MS_TIMELINE=<file> dumps it at ms_destroy)
-    uint32_t *d_prev = nullptr;            // {count, rows} of the nodes each batch bound (x2)
-    int64_t *d_prev_rec = nullptr;         // and their final records (x2)
-    DRow *d_drow = nullptr;                // derived rows of the binary64 sweep (tile_cap * kFullWaveTile)
+    DevBuf<unsigned long long> d_tile_keys;
+    DevBuf<uint32_t> d_tile_flags;
+    DevBuf<unsigned long long> d_spec;     // per-pod speculative winner key (atomicMax target)
+    DevBuf<uint32_t> d_spec_flags;         // per-pod flags of tiles with no feasible row (atomicOr target)
+    DevBuf<unsigned long long> d_top4;     // per-pod global speculative top-4 keys
+    DevBuf<int64_t> d_top4_rec;            // their batch-start node records (validator layout)
+    DevBuf<unsigned long long> d_top_ext;  // ranks 4..7 per pod (the validator's slow pods)
+    DevBuf<uint32_t> d_merge_tags;         // per pod of both merge-output sets: the in-step merge's tag
+    uint32_t merge_tag = 0;                // last in-step merge tag issued
+    DevBuf<unsigned long long> d_tl;       // MS_VSTAMPS: step timeline (MS_TIMELINE=<file> dumps it at ms_destroy)
+    DevBuf<uint32_t> d_prev;               // {count, rows} of the nodes each batch bound (x2)
+    DevBuf<int64_t> d_prev_rec;            // and their final records (x2)
+    DevBuf<DRow> d_drow;                   // derived rows of the binary64 sweep (tile_cap * kFullWaveTile)
     // (every sequential-engine buffer above is double-buffered by batch parity)
-    // ms_schedule_batch's chunked copies (schedule_chunked): H2D / D2H of host arrays beside the cycle
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_copy[4] = {nullptr, nullptr, nullptr, nullptr}, ev_cyc[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev_copy[4], ev_cyc[4];  // per chunk of a host-array call (ensure_chunk_events)
     uint32_t tile_cap = 0;  // tiles allocated per pod
-    uint32_t *d_overflow = nullptr;
-    ms_pod_compact *h_podz = nullptr;      // pinned compact pods / results the compact cycle's
-    ms_result_compact *h_resz = nullptr;   // kernel reads and writes over PCIe (zero-copy)
+    DevBuf<uint32_t> d_overflow;
+    PinnedBuf<ms_pod_compact> h_podz;     // pinned compact pods / results the compact cycle's
+    PinnedBuf<ms_result_compact> h_resz;  // kernel reads and writes over PCIe (zero-copy)
     uint32_t z_cap = 0;
     // MS_PLUGINS_NU_TT_NN: segment summaries of the sweep (tt_bytes allocated)
-    void *d_tt = nullptr;
+    DevBuf<void> d_tt;
     size_t tt_bytes = 0;
     // d_tt is one scratch for every TT cycle of the context: a cycle on another
     // stream than the previous one waits for ev_tt, recorded after that one's
     // combine (node-sharded submits run on caller / sweep streams that are not
     // chained through the context stream)
-    hipEvent_t ev_tt = nullptr;
-    hipStream_t tt_stream = nullptr;
+    Event ev_tt;
+    hipStream_t tt_stream = nullptr;  // (not owned: the context's, a caller's or the communicator's)
     // MS_PLUGINS_NU_NN_NAM: the registered term sets as lookup tables (NamTab) and the
     // per-class passes' scratch of a chunk (nam_bytes allocated)
-    void *d_terms = nullptr;
+    DevBuf<void> d_terms;
     uint32_t n_terms = 0, terms_cap = 0;
-    void *d_nam = nullptr;
+    DevBuf<void> d_nam;
     size_t nam_bytes = 0;
     // node-sharded sequential mode: merged candidate lists (ms_seq_validate_device)
-    ms_seq_cand *d_merged = nullptr;
-    uint32_t *d_merged_flags = nullptr;
-
+    DevBuf<ms_seq_cand> d_merged;
+    DevBuf<uint32_t> d_merged_flags;
 
     // Ordering. Every piece of work that reads or writes the node table or the
     // context's scratch is totally ordered through the context stream: a call
@@ -121,10 +182,9 @@ struct ms_ctx {
     // communicator's in-flight sweeps (table readers on its internal streams,
     // comm_fence_reads); a stream ordered before the last fence must wait again
     uint64_t fence_seq = 0, ordered_fence = 0;
-    hipStream_t ordered_stream = nullptr;
+    hipStream_t ordered_stream = nullptr;  // (not owned: a caller's)
     uint64_t ordered_seq = 0;
-    hipEvent_t ev_order = nullptr;
-    hipEvent_t ev_back = nullptr;
+    Event ev_order, ev_back;
 
     // RCCL communicator and the node-sharded pipelines (ms_comm.cpp); null
     // until ms_comm_init

@@ -136,6 +136,21 @@ def test_copy_pool_tsan(tmp_path):
     assert "0 failed" in _run([exe], env=env)
 
 
+def test_owned_asan(tmp_path):
+    # the owner of every device / pinned buffer, event and stream (csrc/ms_owned.h, the copy ms_ctx.h
+    # instantiates with the HIP calls) over a counting malloc/free policy: one release per block through
+    # moves, re-allocation, failure at every position of an 11-buffer group and the retry after it;
+    # ASan's double-free and leak detection is the judge
+    exe = str(tmp_path / "test_owned")
+    src = os.path.join(ROOT, "tests", "cpp", "test_owned.cpp")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+                    "-I", os.path.join(PKG, "csrc"), src, "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = _run([exe], env=env)
+    print(out)
+    assert out.splitlines()[-1] == "0 failed", out
+
+
 def test_nam_layout_plan_asan(tmp_path):
     # the NodeAffinity scratch plan (csrc/ms_nam_layout.h, the copy ms_affinity.hip and ms_capi.cpp
     # use): every chunk of a call, the short last one included, fits the call's allocation; and the
