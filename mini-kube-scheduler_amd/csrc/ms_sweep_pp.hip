@@ -32,6 +32,10 @@
 // layout, and the synthetic clusters'), the pod's digit can only sit at three
 // known slots, so the per-pod mask is one v_bitop3 and the slots need no
 // search: 24 VALU per pod and group instead of 31, same keys bit for bit.
+// Class runs (run_setup): the mask and the candidate rows depend only on the
+// pod's class (fixed slot, tolerates), so a workgroup sorts its pods by class
+// and a wave finds a class's candidates once per run; a pod of the run then
+// costs one add and one mix32 per candidate, 17 VALU per pod and group.
 //
 // Grid: a workgroup holds ALL of the context's rows (up to 16 waves x 64 lanes
 // x kPpWords groups = 122,880 rows; more rows split over grid.y and combine
@@ -225,7 +229,8 @@ __device__ __forceinline__ u64 pod_slow(const Word (&W)[KW], const Word &Wt, boo
 // Pod p of a workgroup's chunk as the prologue leaves it in LDS: x = A =
 // tb_pod(seed32, ordinal), y = class bits (digit, 14 for a non-digit name, |
 // tolerates << 4) | name digit byte << 8 | the fixed slot p0 << 16 ((digit -
-// node_base) mod 10, 30 for a non-digit name: word_fix).
+// node_base) mod 10, 30 for a non-digit name: word_fix). Bits 21-31 of y are
+// free here: the prologue puts the pod's index in the chunk there.
 // pstride: bytes per pod record (sizeof(ms_pod_rec), or 8 for ms_pod_compact,
 // its first 8 bytes).
 __device__ __forceinline__ uint2 pod_entry(const ms_pod_rec *__restrict__ pods, uint32_t p, uint32_t seed32,
@@ -238,7 +243,69 @@ __device__ __forceinline__ uint2 pod_entry(const ms_pod_rec *__restrict__ pods, 
     return make_uint2(tb_pod(seed32, pr.x), info | ((pr.y & 0xFFu) << 8) | (p0 << 16));
 }
 
-// One wave sweeps the chunk's pods [0, np) through its NW words into lds[p].
+// Class runs. A pod's class is (fixed slot p0, tolerates): 20 digit classes,
+// key p0 + 10 * tolerates, and one "other" class (non-digit names). The match
+// mask of a word and the three candidate rows depend on the class alone, so
+// the prologue counting-sorts the chunk's entries by class and the sweep
+// hoists that work out of the pod loop for runs of one class (run_setup).
+// Sorted order: the whole 8-pod blocks of every digit class first, class by
+// class (region A; class c holds positions rb[c] .. rb[c + 1]), then what is
+// left of every class and the other class (region B, rb[20] .. rb[21] = np).
+// Bits 21-31 of an entry's y carry its index in the chunk (np <= kPpMaxChunk
+// = 2048), which the epilogue writes by.
+constexpr uint32_t kPpClasses = 20;
+constexpr uint32_t kPpSortWords = 72;  // LDS words after pinfo: counts, rb, region B cursors (24 each)
+// Chunks below this are swept in arrival order (no sort, one region B): their
+// runs are too short for the run form (20 classes), and the small shards'
+// 2-wave workgroups of 49-56 pods keep their prologue.
+constexpr uint32_t kPpSortMin = 80;
+
+__device__ __forceinline__ uint32_t pod_class(uint32_t info) {
+    const uint32_t p0 = (info >> 16) & 31u;
+    return p0 < 10u ? p0 + ((info & 16u) ? 10u : 0u) : kPpClasses;
+}
+
+// Candidate bases of one class for a wave whose NW words hold at most 3 rows
+// of a digit each (not kModeGen): B[3k .. 3k+2] = hb + slot * kG24 for the
+// score-10 rows of word k (match10, which on digit-aligned words is match_fix
+// at the class's slots), fewer than 3 filled by a duplicate as in word_fast.
+// A word with no such row takes a base of another word of the lane, a lane with
+// none the base of the wave's first lane that has one: duplicates of real
+// candidates, which leave every pod's maximum unchanged. Then a pod of the class
+// costs one add and one mix32 per slot and needs no mask. False (wave-uniform)
+// when no row of the wave scores 10 for the class: its pods take the per-pod
+// path, get u == 0 there and are redone by pod_slow.
+template <int KW, int NW>
+__device__ __forceinline__ bool run_setup(const Word (&W)[KW], uint32_t info, uint32_t (&B)[NW * 3]) {
+    const Pod qc = pod_bits(0u, info);
+    uint32_t m[NW], fb = 0;
+    bool has = false;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        m[k] = match10(W[k], qc);
+        const int i0 = (int)first_slot(m[k]);
+        const int i2 = 31 - (int)last_lz(m[k]);
+        const int i1 = max((int)first_slot(m[k] & (m[k] - 1u)), i0);
+        B[3 * k + 0] = __umul24((uint32_t)i0, kG24) + W[k].hb;
+        B[3 * k + 1] = __umul24((uint32_t)i1, kG24) + W[k].hb;
+        B[3 * k + 2] = __umul24((uint32_t)i2, kG24) + W[k].hb;
+        if (m[k] != 0u && !has) fb = B[3 * k];
+        has = has || m[k] != 0u;
+    }
+    const u64 any = __ballot(has);
+    if (any == 0ull) return false;
+    const uint32_t fbw = (uint32_t)__builtin_amdgcn_readlane((int)fb, (int)__builtin_ctzll(any));
+    if (!has) fb = fbw;
+#pragma unroll
+    for (int k = 0; k < NW; ++k)
+        if (m[k] == 0u) B[3 * k + 0] = B[3 * k + 1] = B[3 * k + 2] = fb;
+    return true;
+}
+
+// One wave sweeps the chunk's pods [beg, end) (beg a multiple of 8) through its
+// NW words into lds[p]. form (wave-uniform): the range is a run of one class
+// whose candidate bases are B (run_setup); else every pod is evaluated by its
+// own bits.
 // tpt != 0: the wave also holds the workgroup's packed last word Wt, whose
 // T <= 64 / tpt groups repeat in tpt lane segments of 64 / tpt lanes: segment
 // i evaluates pod i of a group of tpt pods (its bits from the lanes' block
@@ -252,13 +319,15 @@ __device__ __forceinline__ uint2 pod_entry(const ms_pod_rec *__restrict__ pods, 
 // kModeFix (every group of the wave is digit-aligned: word_fix).
 constexpr int kModeFast = 0, kModeGen = 1, kModeFix = 2;
 
-template <int KW, int NW, int MODE, bool TAIL>
-__device__ __forceinline__ void sweep_range(const Word (&W)[KW], const Word &Wt, uint32_t tpt, uint32_t tshare,
-                                            uint32_t tidx, const uint2 *pinfo, uint32_t np, uint32_t lane, u64 *lds) {
+template <int KW, int NW, int MODE, bool TAIL, int NB>
+__device__ __forceinline__ void sweep_pods(const Word (&W)[KW], const Word &Wt, uint32_t tpt, uint32_t tshare,
+                                           uint32_t tidx, const uint2 *pinfo, uint32_t beg, uint32_t end, bool form,
+                                           const uint32_t (&B)[NB], uint32_t lane, u64 *lds) {
     constexpr bool GEN = MODE == kModeGen;
+    constexpr bool RUN = NB > 1;  // the run form is compiled in (NB = 3 * NW)
     const uint32_t seg_shift = tpt == 8u ? 3u : tpt == 4u ? 4u : 5u;  // log2(64 / tpt)
-    for (uint32_t pb = 0; pb < np; pb += 64) {
-        const uint32_t nblk = min(64u, np - pb);
+    for (uint32_t pb = beg; pb < end; pb += 64) {
+        const uint32_t nblk = min(64u, end - pb);
         // the block's pods, one per lane: A and digit | tolerates << 4
         uint32_t a_l = 0, info_l = 14u | (30u << 16);  // (lanes past the block: no row matches)
         if (lane < nblk) {
@@ -267,21 +336,33 @@ __device__ __forceinline__ void sweep_range(const Word (&W)[KW], const Word &Wt,
             info_l = e.y;
         }
         for (uint32_t j = 0; j < nblk; j += 8) {
-            Pod q[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t)
-                q[t] = pod_bits((uint32_t)__builtin_amdgcn_readlane((int)a_l, (int)(j + t)),
-                                (uint32_t)__builtin_amdgcn_readlane((int)info_l, (int)(j + t)));
             uint32_t r[8];
+            if (RUN && form) {
+                // a whole block of one class: every slot holds a candidate
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                uint32_t h = 0;
+                for (int t = 0; t < 8; ++t) {
+                    const uint32_t A = (uint32_t)__builtin_amdgcn_readlane((int)a_l, (int)(j + t));
+                    uint32_t h = 0;
 #pragma unroll
-                for (int k = 0; k < NW; ++k)
-                    h = max(h, MODE == kModeGen ? word_scan(match10(W[k], q[t]), W[k].hb + q[t].A)
-                               : MODE == kModeFix ? word_fix(W[k], q[t])
-                                                  : word_fast(W[k], q[t]));
-                r[t] = h;
+                    for (int i = 0; i < NB; ++i) h = max(h, mix32(B[i] + A));
+                    r[t] = h;
+                }
+            } else {
+                Pod q[8];
+#pragma unroll
+                for (int t = 0; t < 8; ++t)
+                    q[t] = pod_bits((uint32_t)__builtin_amdgcn_readlane((int)a_l, (int)(j + t)),
+                                    (uint32_t)__builtin_amdgcn_readlane((int)info_l, (int)(j + t)));
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    uint32_t h = 0;
+#pragma unroll
+                    for (int k = 0; k < NW; ++k)
+                        h = max(h, MODE == kModeGen ? word_scan(match10(W[k], q[t]), W[k].hb + q[t].A)
+                                   : MODE == kModeFix ? word_fix(W[k], q[t])
+                                                      : word_fast(W[k], q[t]));
+                    r[t] = h;
+                }
             }
             if (TAIL && ((pb + j) >> 3) % tshare == tidx) {  // wave-uniform
                 const uint32_t seg = lane >> seg_shift;
@@ -314,6 +395,34 @@ __device__ __forceinline__ void sweep_range(const Word (&W)[KW], const Word &Wt,
                 if (lane == 0 && v) atomicMax(&lds[pb + j + t], v);
             }
         }
+    }
+}
+
+// One wave sweeps the chunk's pods [0, np). runs: the entries are class-sorted
+// (rb: the 22 bounds); kModeFix and kModeFast waves then take region A's class
+// runs one by one, in the run form where run_setup finds a candidate, and
+// region B per pod. Every bound but np is a multiple of 8, so every wave cuts
+// the same 8-pod blocks (the packed last word's sharing counts them). Without
+// runs, and for kModeGen waves, the chunk is one per-pod range.
+// (Padding every run to whole blocks instead of sweeping the rests per pod
+// measured 0.5 % slower at config C, profiles/r07a_class_runs_ab.txt.)
+template <int KW, int NW, int MODE, bool TAIL>
+__device__ __forceinline__ void sweep_range(const Word (&W)[KW], const Word &Wt, uint32_t tpt, uint32_t tshare,
+                                            uint32_t tidx, const uint2 *pinfo, const uint32_t *rb, bool runs,
+                                            uint32_t np, uint32_t lane, u64 *lds) {
+    // (not in the 8-word form: with 24 bases more it needs over 128 VGPRs)
+    constexpr bool RUN = MODE != kModeGen && NW > 0 && KW == kPpWords;
+    const bool cut = RUN && runs;
+    for (uint32_t c = cut ? 0u : kPpClasses; c <= kPpClasses; ++c) {
+        const uint32_t beg = cut ? (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c]) : 0u;
+        const uint32_t end = cut ? (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c + 1]) : np;
+        if (beg >= end) continue;
+        uint32_t B[RUN ? NW * 3 : 1] = {};
+        bool form = false;
+        if constexpr (RUN)
+            if (c < kPpClasses)
+                form = run_setup<KW, NW>(W, (uint32_t)__builtin_amdgcn_readfirstlane((int)pinfo[beg].y), B);
+        sweep_pods<KW, NW, MODE, TAIL>(W, Wt, tpt, tshare, tidx, pinfo, beg, end, form, B, lane, lds);
     }
 }
 
@@ -373,7 +482,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     const ms_pod_rec *__restrict__ pods1, uint32_t n_pods1, uint32_t chunk, uint32_t seed32, u64 *__restrict__ keys1,
     int atomic_keys, ms_result *__restrict__ results, uint32_t present, NodeTable tab, int commit,
     uint32_t pstride, ms_result_compact *__restrict__ resc, PpJob2 j2, int fix_ok, uint32_t xtra) {
-    // LDS: one combine slot per pod of the chunk, then the chunk's pod entries
+    // LDS: one combine slot per pod of the chunk, then the chunk's pod entries,
+    // then the kPpSortWords words of the class sort
     // (xtra: workgroups 0 .. xtra-1 take chunk + 8 pods, the balanced split)
     extern __shared__ u64 lds[];
     uint2 *pinfo = reinterpret_cast<uint2 *>(lds + chunk + (xtra ? 8u : 0u));
@@ -387,9 +497,53 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     const uint32_t pbeg = bi * chunk + min(bi, xtra) * 8u;
     const uint32_t pend = min(n_pods, pbeg + chunk + (bi < xtra ? 8u : 0u));
     const uint32_t np = pend > pbeg ? pend - pbeg : 0u;
-    for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
-        lds[i] = 0;
-        pinfo[i] = pod_entry(pods, pbeg + i, seed32, pstride, node_base % 10u);
+    // after the entries: class counts, the sweep's bounds rb, region B's class starts
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(pinfo + chunk + (xtra ? 8u : 0u));
+    uint32_t *rb = cnt + 24, *sb = cnt + 48;
+    const bool runs = KW == kPpWords && chunk >= kPpSortMin;  // (kernel-uniform; KW = 8: no run form)
+    if (!runs) {
+        for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
+            lds[i] = 0;
+            uint2 e = pod_entry(pods, pbeg + i, seed32, pstride, node_base % 10u);
+            e.y |= i << 21;
+            pinfo[i] = e;
+        }
+    } else {
+        // counting sort by class: the unsorted entries wait in the combine slots
+        // (8 bytes each) with their rank in the class, taken with the count
+        if (threadIdx.x < 24u) cnt[threadIdx.x] = 0u;
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
+            uint2 e = pod_entry(pods, pbeg + i, seed32, pstride, node_base % 10u);
+            e.y |= atomicAdd(&cnt[pod_class(e.y)], 1u) << 21;
+            reinterpret_cast<uint2 *>(lds)[i] = e;
+        }
+        __syncthreads();
+        if (threadIdx.x <= kPpClasses) {
+            // region A: the whole 8-pod blocks of the digit classes; region B: the rest
+            uint32_t a = 0, b = 0, na = 0, nb = 0;
+            for (uint32_t c = 0; c < kPpClasses; ++c) {
+                const uint32_t n = cnt[c], full = n & ~7u;
+                if (c == threadIdx.x) a = na, b = nb;
+                na += full;
+                nb += n - full;
+            }
+            if (threadIdx.x == kPpClasses) {
+                a = na, b = nb;
+                rb[kPpClasses + 1] = np;
+            }
+            rb[threadIdx.x] = a;
+            sb[threadIdx.x] = na + b;
+        }
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
+            const uint2 e = reinterpret_cast<const uint2 *>(lds)[i];
+            const uint32_t c = pod_class(e.y), rank = e.y >> 21;
+            const uint32_t full = c < kPpClasses ? rb[c + 1] - rb[c] : 0u;
+            const uint32_t pos = rank < full ? rb[c] + rank : sb[c] + (rank - full);
+            pinfo[pos] = make_uint2(e.x, (e.y & 0x1FFFFFu) | (i << 21));
+            lds[i] = 0;
+        }
     }
 
     // the wave's groups, dealt round-robin over the workgroup's waves so their
@@ -452,7 +606,7 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
 #define MS_PP_CASE1(N, M, T)                                                                                     \
     case 6 * N + 2 * M + T:                                                                                      \
         if constexpr (N <= KW && (N > 0 || T))                                                                   \
-            sweep_range<KW, (N <= KW ? N : KW), M, T>(W, Wt, tpt, tshare, wv - wv_t, pinfo, np, lane, lds);         \
+            sweep_range<KW, (N <= KW ? N : KW), M, T>(W, Wt, tpt, tshare, wv - wv_t, pinfo, rb, runs, np, lane, lds); \
         break;
 #define MS_PP_CASE(N)        \
     MS_PP_CASE1(N, 0, false) \
@@ -480,26 +634,27 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
         const u64 v = lds[i];
         const uint2 pe = pinfo[i];
+        const uint32_t po = pbeg + (pe.y >> 21);  // the pod at (sorted) position i
         u64 key = present ? kKeyListed : 0ull;  // no feasible row: listed or not (decode_key)
         if (v) {
             const uint32_t h = (uint32_t)v;
             key = make_key((uint32_t)(v >> 32) - 1u, h, tb_unhash(pe.x, h));
         }
         if (keys) {
-            if (!atomic_keys) keys[pbeg + i] = key;
-            else if (key) atomicMax(&keys[pbeg + i], key);
+            if (!atomic_keys) keys[po] = key;
+            else if (key) atomicMax(&keys[po], key);
         }
         if (results || resc) {
             const ms_result r = decode_key(key, (int8_t)(pe.y >> 8), nullptr, 0, present);
             if (results) {
-                results[pbeg + i] = r;
+                results[po] = r;
             } else {  // the compact record, straight into the caller's (pinned host) array
                 ms_result_compact rc;
                 rc.node = r.node;
                 rc.score = (uint16_t)r.score;
                 rc.code = (uint8_t)r.code;
                 rc.plugin_mask = (uint8_t)r.plugin_mask;
-                resc[pbeg + i] = rc;
+                resc[po] = rc;
             }
             // assume-on-select in the same launch (ms_schedule_batch / the sequential
             // NU+NN cycle): NodeInfo.AddPod on the winner, which this context owns
@@ -509,7 +664,7 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
                     const ms_pod_rec z = {};
                     add_pod(tab, (uint32_t)r.node - tab.base, z, +1);
                 } else {
-                    add_pod(tab, (uint32_t)r.node - tab.base, pods[pbeg + i], +1);
+                    add_pod(tab, (uint32_t)r.node - tab.base, pods[po], +1);
                 }
             }
         }
@@ -674,7 +829,8 @@ hipError_t sweep_pp_impl(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *
         if (!keys || resc) return hipErrorInvalidValue;
         hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * n_pods, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_sweep_nunn_pp<kPpWords, false>), grid, dim3(64 * W), chunk * (sizeof(u64) + sizeof(uint2)), s, t.planes,
+        hipLaunchKernelGGL((k_sweep_nunn_pp<kPpWords, false>), grid, dim3(64 * W),
+                           chunk * (sizeof(u64) + sizeof(uint2)) + kPpSortWords * sizeof(uint32_t), s, t.planes,
                            t.gcap, n_groups, t.base, pods, n_pods, chunk, seed32, keys, 1, (ms_result *)nullptr, present,
                            t, 0, (uint32_t)sizeof(ms_pod_rec), (ms_result_compact *)nullptr, PpJob2{}, fix_ok, 0u);
         e = hipGetLastError();
@@ -685,7 +841,7 @@ hipError_t sweep_pp_impl(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *
     }
     // done: recorded by the dispatch itself (hipExtLaunchKernel's stop event: no
     // separate event packet between this sweep and the next launch on s)
-    const uint32_t lds = (chunk + (xtra ? 8u : 0u)) * (sizeof(u64) + sizeof(uint2));
+    const uint32_t lds = (chunk + (xtra ? 8u : 0u)) * (sizeof(u64) + sizeof(uint2)) + kPpSortWords * sizeof(uint32_t);
     unsigned long long *kk = (results || resc) ? nullptr : keys;
     const int cm = (results || resc) ? commit : 0;
     // (gy == 1: the workgroup holds every group; the 8-word form stays unpacked: its
