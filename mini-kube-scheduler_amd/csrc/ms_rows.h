@@ -95,8 +95,11 @@ __device__ __forceinline__ PodFull load_pod(const ms_pod_rec &pr, uint32_t seed3
     q.rm = pr.req_memory;
     q.nc = pr.nonzero_milli_cpu;
     q.nm = pr.nonzero_memory;
-    q.n100c = min(q.nc, 1ll << 55) * 100;
-    q.n100m = min(q.nm, 1ll << 55) * 100;
+    // (both operands int64_t: min(long, long long) resolves to the mixed-type overload that
+    // compares AND returns binary64, and the product then rounds to 53 bits once n > 2^53 / 100)
+    constexpr int64_t kN100Max = (int64_t)1 << 55;
+    q.n100c = (q.nc < kN100Max ? q.nc : kN100Max) * 100;
+    q.n100m = (q.nm < kN100Max ? q.nm : kN100Max) * 100;
     q.nfc = (float)q.nc;
     q.nfm = (float)q.nm;
     q.dig = pr.name_digit;

@@ -10,6 +10,10 @@
  * noderesources/least_allocated.go, restated in oracle/ms_oracle.c).
  * Error bound: |x - (X + eps)| <= 402 u, u = 2^-53, so the
  * result is floor(X) while eps > 402 u and eps + 402 u < 1/cap.
+ * This is the CPU proof (gcc's fma and division); the kernels' own v_fma_f64,
+ * __ddiv_rn and v_cvt_u32_f64 take the same kind of cases, both sides of every
+ * k * cap / 100 step, in tests/test_gpu_la_pairs.py (candidates and sequential
+ * tests on the `fast` tables of tests/_la_cases.py).
  * Build: cc -O2 -ffp-contract=off la_f64_exact.c -lm; prints the case count. */
 #include <math.h>
 #include <stdint.h>

@@ -1,7 +1,9 @@
 """The config-E sweep's binary64 LeastAllocated form (ms_rows.h la_r /
 la_a / eval_fast) equals the reference's integer leastRequestedScore on every
-boundary case tests/c/la_f64_exact.c generates (CPU; the GPU parity suite runs
-the kernel itself, tests/test_gpu_parity.py::test_resource_sequential_capacity_forms)."""
+boundary case tests/c/la_f64_exact.c generates (CPU: gcc's fma and division; the
+kernels themselves take both sides of every k * cap / 100 step, pair by pair, in
+tests/test_gpu_la_pairs.py: test_candidates_pairs[fast-None] for eval_fast,
+test_sequential_pairs[fast-*] for eval_tp64 on the derived rows)."""
 import os
 import subprocess
 
