@@ -96,7 +96,7 @@ int flush_locked(ms_ctx *c) {
     MS_HIP(c, hipMemcpyAsync(c->d_deltas, c->h_deltas, sizeof(NodeDelta) * uniq.size(),
                              hipMemcpyHostToDevice, c->stream));
     MS_HIP(c, launch_apply_deltas(c->t, c->d_deltas, (uint32_t)uniq.size(), c->stream));
-    MS_HIP(c, launch_build_planes(c->t, c->d_deltas, (uint32_t)uniq.size(), c->stream));
+    MS_HIP(c, launch_build_planes(c->t, c->d_cand, c->d_deltas, (uint32_t)uniq.size(), c->stream));
     ++c->ctx_seq;
     return MS_OK;
 }
@@ -465,7 +465,7 @@ int sweep_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, unsigned 
         return fail(c, MS_E_INVAL, "multi-term NodeAffinity shards exchange rescale tables first "
                                    "(ms_nam_segment_device, ms_nam_keys_device)");
     if (c->cfg.plugin_set == MS_PLUGINS_NU_NN) {
-        MS_HIP(c, launch_sweep_pp(c->t, c->rows_dev, d_pods, n_pods, seed32, keys, nullptr, c->present_dev,
+        MS_HIP(c, launch_sweep_pp(c->t, c->d_cand, c->rows_dev, d_pods, n_pods, seed32, keys, nullptr, c->present_dev,
                                   c->num_cus, s, 0, done));
         return MS_OK;
     } else if (c->cfg.plugin_set == MS_PLUGINS_NU_NN_NA) {
@@ -515,7 +515,7 @@ int select_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resul
         return MS_OK;
     }
     if (fused && c->rows_dev <= kPpMaxFusedRows) {
-        MS_HIP(c, launch_sweep_pp(c->t, c->rows_dev, d_pods, n_pods, seed32_of(c->cfg.seed), nullptr, d_res,
+        MS_HIP(c, launch_sweep_pp(c->t, c->d_cand, c->rows_dev, d_pods, n_pods, seed32_of(c->cfg.seed), nullptr, d_res,
                                   c->present_dev, c->num_cus, s, commit, done));
         return MS_OK;
     }
@@ -526,7 +526,7 @@ int select_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_resul
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
         if (fused) {
-            MS_HIP(c, launch_sweep_pp(c->t, c->rows_dev, d_pods + s0, nb, seed32_of(c->cfg.seed), c->d_keys,
+            MS_HIP(c, launch_sweep_pp(c->t, c->d_cand, c->rows_dev, d_pods + s0, nb, seed32_of(c->cfg.seed), c->d_keys,
                                       d_res + s0, c->present_dev, c->num_cus, s, commit));
             continue;
         }
@@ -695,7 +695,7 @@ int schedule_zc(ms_ctx *c, const PodIn *pods, uint32_t n, ResOut *out, CallClock
             }
         });
         ck.lap(MS_PH_STAGE_IN);
-        MS_HIP(c, launch_sweep_pp_compact(c->t, c->rows_dev, c->h_podz + beg(i), beg(i + 1) - beg(i),
+        MS_HIP(c, launch_sweep_pp_compact(c->t, c->d_cand, c->rows_dev, c->h_podz + beg(i), beg(i + 1) - beg(i),
                                           seed32_of(c->cfg.seed), c->h_resz + beg(i), c->present_dev, c->num_cus, s));
         MS_HIP(c, hipEventRecord(c->ev_cyc[i], s));
         ck.lap(MS_PH_LAUNCH);
@@ -821,14 +821,14 @@ int ms_create(const ms_config *cfg, ms_ctx **out) {
         for (size_t i = 0; i < sizeof(bytes) / sizeof(bytes[0]); ++i)
             *cols[i] = static_cast<char *>(c->d_table.get()) + off[i];
     t.gcap = (uint32_t)((n + kGroupRows - 1) / kGroupRows);
-    ok = ok && c->d_planes.alloc((size_t)kPlanes * t.gcap);
+    ok = ok && c->d_planes.alloc((size_t)kPlanes * t.gcap) && c->d_cand.alloc(cand_words(t.cap));
     if (!ok) return bail(MS_E_OOM, "node table allocation");
     t.planes = c->d_planes;
     const size_t b = c->batch_cap;
     ok = ensure_stage(c, c->batch_cap) == MS_OK && c->d_keys.alloc(b) && c->d_flags.alloc(b) && c->d_one.alloc(1) &&
          c->d_overflow.alloc(kStatsBytes / sizeof(uint32_t));
     if (!ok) return bail(MS_E_OOM, "staging allocation");
-    if (launch_init_table(t, c->stream) != hipSuccess || launch_build_planes(t, nullptr, 0, c->stream) != hipSuccess)
+    if (launch_init_table(t, c->stream) != hipSuccess || launch_build_planes(t, c->d_cand, nullptr, 0, c->stream) != hipSuccess)
         return bail(MS_E_HIP, "table init launch");
     if (hipMemsetAsync(c->d_overflow, 0, kStatsBytes, c->stream) != hipSuccess) return bail(MS_E_HIP, "memset");
     if (hipStreamSynchronize(c->stream) != hipSuccess) return bail(MS_E_HIP, "table init");

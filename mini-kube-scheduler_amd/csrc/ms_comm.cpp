@@ -428,7 +428,7 @@ int submit_locked(ms_ctx *c, uint32_t n, const ms_pod_rec *pods, ms_result *resu
     if (co) {  // the stashed batch and this one in one launch
         const CommState::Stash st = m.stash;
         m.stash.on = false;
-        MS_HIP(c, launch_sweep_pp2(c->t, c->rows_dev, st.pods, st.n, m.slot[st.si].keys, pods, n, sl.keys,
+        MS_HIP(c, launch_sweep_pp2(c->t, c->d_cand, c->rows_dev, st.pods, st.n, m.slot[st.si].keys, pods, n, sl.keys,
                                    seed32_of(c->cfg.seed), c->present_dev, c->num_cus, X, m.ev_swept[si]));
         host_tick(m, 1, tp);  // the sweep launch
         m.reads_outstanding = true;

@@ -99,6 +99,24 @@ enum : uint32_t {
     kPlanes
 };
 
+// K1 "pp" candidate lists, derived from the planes (k_build_cand after every
+// k_build_planes): for each of the 20 classes c = name digit + 10 * tolerates
+// the hash bases (base + row) * kG24 of the rows a pod of the class can win,
+// i.e. the present rows whose name ends in the digit and that are schedulable
+// or tolerated, in row order. One u32 buffer (the context's d_cand):
+//   [c], c <= 20     first entry of list c; [c + 1] - [c] is its padded length
+//   [21 + c]         its real length (0: no candidate, the list is empty)
+//   [kCandHeader ..] the entries; every list padded to a multiple of kCandTile
+//                    with copies of its first entry (a duplicate candidate
+//                    leaves every pod's maximum unchanged)
+// A row is in at most two lists, so cand_words(cap) words hold any table.
+constexpr uint32_t kCandClasses = 20;
+constexpr uint32_t kCandTile = 192;   // entries per tile: 3 per lane of a wave
+constexpr uint32_t kCandHeader = 64;  // words before the entries
+__host__ __device__ inline size_t cand_words(uint32_t cap) {
+    return (size_t)kCandHeader + 2u * (size_t)cap + kCandClasses * kCandTile;
+}
+
 // One queued node delta (upsert or delete) as it travels to the device.
 struct NodeDelta {
     uint32_t local;   // local row
@@ -201,20 +219,22 @@ hipError_t launch_init_table(const NodeTable &t, hipStream_t s);
 // scratch, needed only above 122,880 rows), and with commit != 0 each winner's
 // NodeInfo.AddPod in the same launch; else keys[i] = this shard's max packed
 // key (0 = none), overwritten. present: global present-node count (decode).
-hipError_t launch_sweep_pp(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+// cand: the table's candidate lists (above), which class-sorted chunks of a
+// one-workgroup-per-chunk launch sweep instead of the planes.
+hipError_t launch_sweep_pp(const NodeTable &t, const uint32_t *cand, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
                            uint32_t seed32, unsigned long long *keys, ms_result *results, uint32_t present,
                            int num_cus, hipStream_t s, int commit = 0, hipEvent_t done = nullptr);
 // Two shard sweeps (keys only, rows <= kPpMaxFusedRows) in ONE launch: the
 // per-launch ramp and drain are paid once for both batches (ms_sharded_submit
 // coalesces consecutive submits). done: recorded after both.
-hipError_t launch_sweep_pp2(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods1, uint32_t n1,
+hipError_t launch_sweep_pp2(const NodeTable &t, const uint32_t *cand, uint32_t n_rows, const ms_pod_rec *pods1, uint32_t n1,
                             unsigned long long *keys1, const ms_pod_rec *pods2, uint32_t n2, unsigned long long *keys2,
                             uint32_t seed32, uint32_t present, int num_cus, hipStream_t s, hipEvent_t done);
 // The compact host-array cycle (ms_schedule_batch_compact) in one launch, rows
 // <= kPpMaxFusedRows: pods are ms_pod_compact records and results
 // ms_result_compact, both in pinned host memory the kernel reads and writes
 // over PCIe (no copy launches, no widen / narrow passes); binds committed.
-hipError_t launch_sweep_pp_compact(const NodeTable &t, uint32_t n_rows, const ms_pod_compact *pods, uint32_t n_pods,
+hipError_t launch_sweep_pp_compact(const NodeTable &t, const uint32_t *cand, uint32_t n_rows, const ms_pod_compact *pods, uint32_t n_pods,
                                    uint32_t seed32, ms_result_compact *results, uint32_t present, int num_cus,
                                    hipStream_t s);
 // (done, optional: recorded after the sweep, by its own dispatch when it is
@@ -222,8 +242,10 @@ hipError_t launch_sweep_pp_compact(const NodeTable &t, uint32_t n_rows, const ms
 // Rows one K1 pp workgroup holds (16 waves x 64 lanes x 4 groups of 30):
 // up to here the single-shard cycle is one launch with no key scratch.
 constexpr uint32_t kPpMaxFusedRows = 16u * 64u * 4u * kGroupRows;
-// Rebuilds the bit planes of the groups touched by deltas (or all groups when d_deltas is null).
-hipError_t launch_build_planes(const NodeTable &t, const NodeDelta *d_deltas, uint32_t n, hipStream_t s);
+// Rebuilds the bit planes of the groups touched by deltas (or all groups when d_deltas
+// is null), then every candidate list (cand: cand_words(t.cap) words) from the planes.
+hipError_t launch_build_planes(const NodeTable &t, uint32_t *cand, const NodeDelta *d_deltas, uint32_t n,
+                               hipStream_t s);
 // keys[0, n) = v (the atomicMax targets of the NodeAffinity / resource sweeps
 // start at kKeyListed when the shard lists a node, else 0)
 hipError_t launch_fill_keys(unsigned long long *keys, uint32_t n, unsigned long long v, hipStream_t s);

@@ -36,6 +36,12 @@
 // pod's class (fixed slot, tolerates), so a workgroup sorts its pods by class
 // and a wave finds a class's candidates once per run; a pod of the run then
 // costs one add and one mix32 per candidate, 17 VALU per pod and group.
+// Candidate lists (sweep_lists): the candidate rows of a class depend only on
+// the node table, so k_build_cand lists them once per flush, beside the planes
+// (ms_internal.h kCand*). Where one workgroup holds every row (grid.y == 1) a
+// sorted chunk's digit classes are swept over the class's dense list, 192
+// entries to a wave and tile, whatever the rows' layout; the planes then serve
+// only pods without a digit and classes with no candidate.
 //
 // Grid: a workgroup holds ALL of the context's rows (up to 16 waves x 64 lanes
 // x kPpWords groups = 122,880 rows; more rows split over grid.y and combine
@@ -251,10 +257,13 @@ __device__ __forceinline__ uint2 pod_entry(const ms_pod_rec *__restrict__ pods, 
 // Sorted order: the whole 8-pod blocks of every digit class first, class by
 // class (region A; class c holds positions rb[c] .. rb[c + 1]), then what is
 // left of every class and the other class (region B, rb[20] .. rb[21] = np).
+// A chunk swept in the list form has no rests: region A holds every digit
+// class whole, at any length, and region B the other class alone.
 // Bits 21-31 of an entry's y carry its index in the chunk (np <= kPpMaxChunk
 // = 2048), which the epilogue writes by.
 constexpr uint32_t kPpClasses = 20;
-constexpr uint32_t kPpSortWords = 72;  // LDS words after pinfo: counts, rb, region B cursors (24 each)
+// LDS words after pinfo: counts, rb, region B cursors, the candidate lists' 21 offsets (24 each)
+constexpr uint32_t kPpSortWords = 96;
 // Chunks below this are swept in arrival order (no sort, one region B): their
 // runs are too short for the run form (20 classes), and the small shards'
 // 2-wave workgroups of 49-56 pods keep their prologue.
@@ -398,29 +407,122 @@ __device__ __forceinline__ void sweep_pods(const Word (&W)[KW], const Word &Wt, 
     }
 }
 
+// The list form. Tiles (kCandTile entries, 3 per lane) of the list of the class
+// whose pods carry class bits info: their count, and with off the list's first
+// entry; 0 for a class with no candidate. hdr: the buffer's header (in LDS).
+__device__ __forceinline__ uint32_t list_tiles(const uint32_t *hdr, uint32_t info, uint32_t *off) {
+    const uint32_t y = (uint32_t)__builtin_amdgcn_readfirstlane((int)info);
+    const uint32_t lc = (y & 15u) + ((y & 16u) ? kCandClasses / 2u : 0u);  // digit + 10 * tolerates
+    const uint32_t o = (uint32_t)__builtin_amdgcn_readfirstlane((int)hdr[lc]);
+    if (off) *off = o;
+    return ((uint32_t)__builtin_amdgcn_readfirstlane((int)hdr[lc + 1]) - o) / kCandTile;
+}
+
+// One wave sweeps the pods [beg, end) of one class through NT tiles of the
+// class's list, B[3k .. 3k+2] the lane's entries of tile k: one add and one
+// mix32 per pod and entry. Every entry is a candidate of every pod of the
+// class (or a copy of one), so the maximum stands as it is, also when it is 0:
+// that is the hash of a real candidate then, and no redo is needed.
+// The range may start anywhere and its last block hold fewer than 8 pods,
+// whose absent pods are not hashed (wave-uniform tests).
+template <int NT>
+__device__ __forceinline__ void sweep_list_pods(const uint32_t (&B)[3 * kPpWords], const uint2 *pinfo, uint32_t beg,
+                                                uint32_t end, uint32_t lane, u64 *lds) {
+    for (uint32_t pb = beg; pb < end; pb += 64) {
+        const uint32_t nblk = min(64u, end - pb);
+        const uint32_t a_l = lane < nblk ? pinfo[pb + lane].x : 0u;
+        for (uint32_t j = 0; j < nblk; j += 8) {
+            uint32_t r[8];
+            if (nblk - j >= 8u) {
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    const uint32_t A = (uint32_t)__builtin_amdgcn_readlane((int)a_l, (int)(j + t));
+                    uint32_t h = 0;
+#pragma unroll
+                    for (int i = 0; i < 3 * NT; ++i) h = max(h, mix32(B[i] + A));
+                    r[t] = h;
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    r[t] = 0;
+                    if (j + (uint32_t)t < nblk) {
+                        const uint32_t A = (uint32_t)__builtin_amdgcn_readlane((int)a_l, (int)(j + t));
+#pragma unroll
+                        for (int i = 0; i < 3 * NT; ++i) r[t] = max(r[t], mix32(B[i] + A));
+                    }
+                }
+            }
+            const uint32_t u = reduce8(r, lane);
+            const uint32_t pi = j + rev3(lane >> 3);  // lanes 8k: pod pi of the block
+            if ((lane & 7u) == 0u && pi < nblk) atomicMax(&lds[pb + pi], (11ull << 32) | u);
+        }
+    }
+}
+
+// One wave's share of a class-sorted chunk in the list form: of every digit
+// class with candidates, wave wv takes tiles wv, wv + waves, .. of the class's
+// list, up to kPpWords of them per pass over the class's pods (a list of more
+// than kPpWords * waves tiles takes further passes; the waves combine by
+// atomicMax on LDS either way). A wave with no tile of a class skips it.
+__device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, const uint32_t *hdr,
+                                            const uint2 *pinfo, const uint32_t *rb, uint32_t wv, uint32_t waves,
+                                            uint32_t lane, u64 *lds) {
+    for (uint32_t c = 0; c < kPpClasses; ++c) {
+        const uint32_t beg = (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c]);
+        const uint32_t end = (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c + 1]);
+        if (beg >= end) continue;
+        uint32_t off;
+        const uint32_t ntile = list_tiles(hdr, pinfo[beg].y, &off);
+        for (uint32_t t0 = wv; t0 < ntile; t0 += kPpWords * waves) {
+            const uint32_t nt = min((uint32_t)kPpWords, (ntile - t0 + waves - 1u) / waves);  // >= 1
+            uint32_t B[3 * kPpWords];
+#pragma unroll
+            for (int k = 0; k < kPpWords; ++k) {
+                const uint32_t *e = cand + kCandHeader + off + (t0 + k * waves) * kCandTile + lane;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) B[3 * k + i] = (uint32_t)k < nt ? e[i * 64] : 0u;
+            }
+            switch (nt) {  // wave-uniform
+                case 1: sweep_list_pods<1>(B, pinfo, beg, end, lane, lds); break;
+                case 2: sweep_list_pods<2>(B, pinfo, beg, end, lane, lds); break;
+                case 3: sweep_list_pods<3>(B, pinfo, beg, end, lane, lds); break;
+                default: sweep_list_pods<4>(B, pinfo, beg, end, lane, lds); break;
+            }
+        }
+    }
+}
+
 // One wave sweeps the chunk's pods [0, np). runs: the entries are class-sorted
 // (rb: the 22 bounds); kModeFix and kModeFast waves then take region A's class
 // runs one by one, in the run form where run_setup finds a candidate, and
 // region B per pod. Every bound but np is a multiple of 8, so every wave cuts
 // the same 8-pod blocks (the packed last word's sharing counts them). Without
 // runs, and for kModeGen waves, the chunk is one per-pod range.
+// lists: the chunk is swept in the list form (sweep_lists takes every digit
+// class whose list hdr, the buffer's header, shows non-empty): what is left
+// here, for waves of every mode, are the digit classes with no candidate and
+// the other class, per pod. Their ranges start anywhere; the packed last
+// word's sharing only needs every wave to cut the same blocks, which they do
+// (the same beg for all).
 // (Padding every run to whole blocks instead of sweeping the rests per pod
 // measured 0.5 % slower at config C, profiles/r07a_class_runs_ab.txt.)
 template <int KW, int NW, int MODE, bool TAIL>
 __device__ __forceinline__ void sweep_range(const Word (&W)[KW], const Word &Wt, uint32_t tpt, uint32_t tshare,
                                             uint32_t tidx, const uint2 *pinfo, const uint32_t *rb, bool runs,
-                                            uint32_t np, uint32_t lane, u64 *lds) {
+                                            bool lists, const uint32_t *hdr, uint32_t np, uint32_t lane, u64 *lds) {
     // (not in the 8-word form: with 24 bases more it needs over 128 VGPRs)
     constexpr bool RUN = MODE != kModeGen && NW > 0 && KW == kPpWords;
-    const bool cut = RUN && runs;
+    const bool cut = lists || (RUN && runs);
     for (uint32_t c = cut ? 0u : kPpClasses; c <= kPpClasses; ++c) {
         const uint32_t beg = cut ? (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c]) : 0u;
         const uint32_t end = cut ? (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c + 1]) : np;
         if (beg >= end) continue;
+        if (lists && c < kPpClasses && list_tiles(hdr, pinfo[beg].y, nullptr) != 0u) continue;
         uint32_t B[RUN ? NW * 3 : 1] = {};
         bool form = false;
         if constexpr (RUN)
-            if (c < kPpClasses)
+            if (!lists && c < kPpClasses)
                 form = run_setup<KW, NW>(W, (uint32_t)__builtin_amdgcn_readfirstlane((int)pinfo[beg].y), B);
         sweep_pods<KW, NW, MODE, TAIL>(W, Wt, tpt, tshare, tidx, pinfo, beg, end, form, B, lane, lds);
     }
@@ -481,7 +583,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     const uint32_t *__restrict__ planes, uint32_t gstride, uint32_t n_groups, uint32_t node_base,
     const ms_pod_rec *__restrict__ pods1, uint32_t n_pods1, uint32_t chunk, uint32_t seed32, u64 *__restrict__ keys1,
     int atomic_keys, ms_result *__restrict__ results, uint32_t present, NodeTable tab, int commit,
-    uint32_t pstride, ms_result_compact *__restrict__ resc, PpJob2 j2, int fix_ok, uint32_t xtra) {
+    uint32_t pstride, ms_result_compact *__restrict__ resc, PpJob2 j2, int fix_ok, uint32_t xtra,
+    const uint32_t *__restrict__ cand) {
     // LDS: one combine slot per pod of the chunk, then the chunk's pod entries,
     // then the kPpSortWords words of the class sort
     // (xtra: workgroups 0 .. xtra-1 take chunk + 8 pods, the balanced split)
@@ -499,8 +602,11 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     const uint32_t np = pend > pbeg ? pend - pbeg : 0u;
     // after the entries: class counts, the sweep's bounds rb, region B's class starts
     uint32_t *cnt = reinterpret_cast<uint32_t *>(pinfo + chunk + (xtra ? 8u : 0u));
-    uint32_t *rb = cnt + 24, *sb = cnt + 48;
+    uint32_t *rb = cnt + 24, *sb = cnt + 48, *hdr = cnt + 72;
     const bool runs = KW == kPpWords && chunk >= kPpSortMin;  // (kernel-uniform; KW = 8: no run form)
+    // the list form: this workgroup holds every row (else the workgroups of a chunk
+    // would each sweep the whole list)
+    const bool lists = runs && cand != nullptr && gridDim.y == 1u;
     if (!runs) {
         for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
             lds[i] = 0;
@@ -512,6 +618,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
         // counting sort by class: the unsorted entries wait in the combine slots
         // (8 bytes each) with their rank in the class, taken with the count
         if (threadIdx.x < 24u) cnt[threadIdx.x] = 0u;
+        if (lists)
+            for (uint32_t i = threadIdx.x; i <= kCandClasses; i += blockDim.x) hdr[i] = cand[i];
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
             uint2 e = pod_entry(pods, pbeg + i, seed32, pstride, node_base % 10u);
@@ -520,10 +628,11 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
         }
         __syncthreads();
         if (threadIdx.x <= kPpClasses) {
-            // region A: the whole 8-pod blocks of the digit classes; region B: the rest
+            // region A: the whole 8-pod blocks of the digit classes (the list form: all
+            // their pods); region B: the rest
             uint32_t a = 0, b = 0, na = 0, nb = 0;
             for (uint32_t c = 0; c < kPpClasses; ++c) {
-                const uint32_t n = cnt[c], full = n & ~7u;
+                const uint32_t n = cnt[c], full = lists ? n : n & ~7u;
                 if (c == threadIdx.x) a = na, b = nb;
                 na += full;
                 nb += n - full;
@@ -606,7 +715,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
 #define MS_PP_CASE1(N, M, T)                                                                                     \
     case 6 * N + 2 * M + T:                                                                                      \
         if constexpr (N <= KW && (N > 0 || T))                                                                   \
-            sweep_range<KW, (N <= KW ? N : KW), M, T>(W, Wt, tpt, tshare, wv - wv_t, pinfo, rb, runs, np, lane, lds); \
+            sweep_range<KW, (N <= KW ? N : KW), M, T>(W, Wt, tpt, tshare, wv - wv_t, pinfo, rb, runs, lists, hdr, np, \
+                                                      lane, lds);                                               \
         break;
 #define MS_PP_CASE(N)        \
     MS_PP_CASE1(N, 0, false) \
@@ -630,6 +740,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
                 break;  // no groups in this wave
         }
     }
+    if constexpr (KW == kPpWords)
+        if (np && lists) sweep_lists(cand, hdr, pinfo, rb, wv, waves, lane, lds);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
         const u64 v = lds[i];
@@ -670,6 +782,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
         }
     }
 }
+
+__host__ __device__ inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 // Bit planes of one 30-row group from the SoA columns (flags, digit).
 __device__ __forceinline__ void build_group(const NodeTable &t, uint32_t g) {
@@ -718,15 +832,91 @@ __global__ void k_build_planes(NodeTable t, const NodeDelta *__restrict__ deltas
     if (g < t.gcap) build_group(t, g);
 }
 
-inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+// The rows of group g that a pod of list class c (digit + 10 * tolerates) can win: match10's mask.
+__device__ __forceinline__ uint32_t cand_mask(const NodeTable &t, uint32_t g, uint32_t c) {
+    const uint32_t st = t.gcap, v = c % 10u;
+    const uint32_t d0 = t.planes[kPlaneD0 * st + g], d1 = t.planes[kPlaneD1 * st + g];
+    const uint32_t d2 = t.planes[kPlaneD2 * st + g], d3 = t.planes[kPlaneD3 * st + g];
+    const uint32_t f = t.planes[(c >= 10u ? kPlanePresent : kPlaneSched) * st + g];
+    return f & ((v & 1u) ? d0 : ~d0) & ((v & 2u) ? d1 : ~d1) & ((v & 4u) ? d2 : ~d2) & ((v & 8u) ? d3 : ~d3);
+}
+
+// The candidate lists (ms_internal.h kCand*) from the planes: block c builds
+// list c. Every block first counts all 20 lists (its list starts after the
+// padded lengths of those before it), then writes its entries in row order:
+// 1024 groups at a time, each thread one group, placed by a block-wide prefix
+// sum of the groups' candidate counts.
+constexpr uint32_t kCandThreads = 1024;
+
+__global__ __launch_bounds__(kCandThreads) void k_build_cand(NodeTable t, uint32_t *__restrict__ cand) {
+    __shared__ uint32_t cnt[kCandClasses], wsum[kCandThreads / 64], first;
+    const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    if (tid < kCandClasses) cnt[tid] = 0u;
+    __syncthreads();
+    uint32_t n[kCandClasses] = {};
+    for (uint32_t g = tid; g < t.gcap; g += kCandThreads) {
+#pragma unroll
+        for (uint32_t k = 0; k < kCandClasses; ++k) n[k] += (uint32_t)__popc(cand_mask(t, g, k));
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kCandClasses; ++k) {
+        const uint32_t sum = wave_sum_u32_dpp(n[k]);
+        if (lane == 0u && sum) atomicAdd(&cnt[k], sum);
+    }
+    __syncthreads();
+    uint32_t off = 0;
+    for (uint32_t k = 0; k < c; ++k) off += cdiv(cnt[k], kCandTile) * kCandTile;
+    const uint32_t len = cnt[c], padded = cdiv(len, kCandTile) * kCandTile;
+    if (tid == 0u) {
+        cand[c] = off;
+        cand[kCandClasses + 1u + c] = len;
+        if (c + 1u == kCandClasses) cand[kCandClasses] = off + padded;
+    }
+    uint32_t *ent = cand + kCandHeader + off;
+    uint32_t done = 0;  // entries written by the groups before g0
+    for (uint32_t g0 = 0; g0 < t.gcap; g0 += kCandThreads) {
+        const uint32_t g = g0 + tid;
+        uint32_t m = g < t.gcap ? cand_mask(t, g, c) : 0u;
+        const uint32_t k = (uint32_t)__popc(m);
+        uint32_t incl = k;  // inclusive prefix sum over the wave
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63u) wsum[wv] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < kCandThreads / 64; ++w) {
+            if (w < wv) before += wsum[w];
+            total += wsum[w];
+        }
+        uint32_t pos = done + before + incl - k;
+        while (m) {
+            const uint32_t slot = (uint32_t)__builtin_ctz(m);
+            m &= m - 1u;
+            const uint32_t e = (t.base + g * kGroupRows + slot) * kG24;
+            if (pos == 0u) first = e;
+            if (pos < len) ent[pos] = e;  // (always: the counts come from the same planes)
+            ++pos;
+        }
+        done += total;
+        __syncthreads();
+    }
+    for (uint32_t i = len + tid; i < padded; i += kCandThreads) ent[i] = first;
+}
 
 }  // namespace
 
-hipError_t launch_build_planes(const NodeTable &t, const NodeDelta *d_deltas, uint32_t n, hipStream_t s) {
+hipError_t launch_build_planes(const NodeTable &t, uint32_t *cand, const NodeDelta *d_deltas, uint32_t n,
+                               hipStream_t s) {
     if (!t.planes) return hipSuccess;
     if (!d_deltas) n = t.gcap;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_build_planes, dim3(cdiv(n, 256)), dim3(256), 0, s, t, d_deltas, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !cand) return e;
+    hipLaunchKernelGGL(k_build_cand, dim3(kCandClasses), dim3(kCandThreads), 0, s, t, cand);
     return hipGetLastError();
 }
 
@@ -737,7 +927,7 @@ hipError_t launch_build_planes(const NodeTable &t, const NodeDelta *d_deltas, ui
 constexpr uint32_t kPpMaxChunk = 2048;
 
 namespace {
-hipError_t sweep_pp_impl(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
                          uint32_t seed32, unsigned long long *keys, ms_result *results, uint32_t present, int num_cus,
                          hipStream_t s, int commit, hipEvent_t done, uint32_t pstride, ms_result_compact *resc,
                          const ms_pod_rec *pods2 = nullptr, uint32_t n_pods2 = 0, unsigned long long *keys2 = nullptr) {
@@ -832,7 +1022,8 @@ hipError_t sweep_pp_impl(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *
         hipLaunchKernelGGL((k_sweep_nunn_pp<kPpWords, false>), grid, dim3(64 * W),
                            chunk * (sizeof(u64) + sizeof(uint2)) + kPpSortWords * sizeof(uint32_t), s, t.planes,
                            t.gcap, n_groups, t.base, pods, n_pods, chunk, seed32, keys, 1, (ms_result *)nullptr, present,
-                           t, 0, (uint32_t)sizeof(ms_pod_rec), (ms_result_compact *)nullptr, PpJob2{}, fix_ok, 0u);
+                           t, 0, (uint32_t)sizeof(ms_pod_rec), (ms_result_compact *)nullptr, PpJob2{}, fix_ok, 0u,
+                           (const uint32_t *)nullptr);
         e = hipGetLastError();
         if (e == hipSuccess && results) e = launch_decode(pods, n_pods, keys, nullptr, present, results, s);
         if (e == hipSuccess && results && commit) e = launch_apply_binds(t, pods, n_pods, results, s);
@@ -850,7 +1041,7 @@ hipError_t sweep_pp_impl(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *
 #define MS_PP_LAUNCH(KWV, TPV)                                                                                     \
     hipExtLaunchKernelGGL((k_sweep_nunn_pp<KWV, TPV>), grid, dim3(64 * W), lds, s, nullptr, done, 0, t.planes, t.gcap, \
                           n_groups, t.base, pods, n_pods, chunk, seed32, kk, 0, results, present, t, cm, pstride, resc, j2, \
-                          fix_ok, xtra)
+                          fix_ok, xtra, cand)
     if (KW == (uint32_t)kPpWordsSmall) {
         MS_PP_LAUNCH(kPpWordsSmall, false);
     } else {
@@ -862,27 +1053,27 @@ hipError_t sweep_pp_impl(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *
 }
 }  // namespace
 
-hipError_t launch_sweep_pp(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+hipError_t launch_sweep_pp(const NodeTable &t, const uint32_t *cand, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
                            uint32_t seed32, unsigned long long *keys, ms_result *results, uint32_t present,
                            int num_cus, hipStream_t s, int commit, hipEvent_t done) {
-    return sweep_pp_impl(t, n_rows, pods, n_pods, seed32, keys, results, present, num_cus, s, commit, done,
+    return sweep_pp_impl(t, cand, n_rows, pods, n_pods, seed32, keys, results, present, num_cus, s, commit, done,
                          (uint32_t)sizeof(ms_pod_rec), nullptr);
 }
 
-hipError_t launch_sweep_pp2(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods1, uint32_t n1,
+hipError_t launch_sweep_pp2(const NodeTable &t, const uint32_t *cand, uint32_t n_rows, const ms_pod_rec *pods1, uint32_t n1,
                             unsigned long long *keys1, const ms_pod_rec *pods2, uint32_t n2, unsigned long long *keys2,
                             uint32_t seed32, uint32_t present, int num_cus, hipStream_t s, hipEvent_t done) {
     if (n_rows > kPpMaxFusedRows) return hipErrorInvalidValue;
-    return sweep_pp_impl(t, n_rows, pods1, n1, seed32, keys1, nullptr, present, num_cus, s, 0, done,
+    return sweep_pp_impl(t, cand, n_rows, pods1, n1, seed32, keys1, nullptr, present, num_cus, s, 0, done,
                          (uint32_t)sizeof(ms_pod_rec), nullptr, pods2, n2, keys2);
 }
 
-hipError_t launch_sweep_pp_compact(const NodeTable &t, uint32_t n_rows, const ms_pod_compact *pods, uint32_t n_pods,
+hipError_t launch_sweep_pp_compact(const NodeTable &t, const uint32_t *cand, uint32_t n_rows, const ms_pod_compact *pods, uint32_t n_pods,
                                    uint32_t seed32, ms_result_compact *results, uint32_t present, int num_cus,
                                    hipStream_t s) {
     static_assert(sizeof(ms_pod_compact) == 8 && sizeof(ms_result_compact) == 8, "compact records");
     if (n_rows > kPpMaxFusedRows || !results) return hipErrorInvalidValue;
-    return sweep_pp_impl(t, n_rows, reinterpret_cast<const ms_pod_rec *>(pods), n_pods, seed32, nullptr, nullptr,
+    return sweep_pp_impl(t, cand, n_rows, reinterpret_cast<const ms_pod_rec *>(pods), n_pods, seed32, nullptr, nullptr,
                          present, num_cus, s, 1, nullptr, (uint32_t)sizeof(ms_pod_compact), results);
 }
 
