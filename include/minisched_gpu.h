@@ -69,9 +69,10 @@ extern "C" {
  * PreferNoSchedule ids only tolerations with that or an empty effect can).
  * (k8s@v1.22.0 plugins/tainttoleration/taint_toleration.go, restated.) */
 #define MS_PLUGINS_NU_TT_NN 3
-/* Filter[NU]; Score[NN (weight w0), NodeAffinity with SEVERAL preferred terms
- * (weight w1), ScoreExtensions = DefaultNormalizeScore(MaxNodeScore,
- * reverse=false) run by the in-loop hook exactly as written]. A pod's terms are
+/* Filter[NU, NodeAffinity (nodeSelector and required terms, ms_nam_required_sets)];
+ * Score[NN (weight w0), NodeAffinity with SEVERAL preferred terms (weight w1),
+ * ScoreExtensions = DefaultNormalizeScore(MaxNodeScore, reverse=false) run by
+ * the in-loop hook over the feasible nodes exactly as written]. A pod's terms are
  * a term set (ms_nam_term_set / ms_nam_term_set_ext) registered with
  * ms_nam_term_sets(_ext); the pod record
  * names it by id = pref_zone | pref_weight << 8 (0 = no terms). Raw scores are
@@ -97,6 +98,7 @@ extern "C" {
 #define MS_MASK_NODE_UNSCHEDULABLE (1u << 0) /* "NodeUnschedulable" */
 #define MS_MASK_NODE_RESOURCES_FIT (1u << 1) /* "NodeResourcesFit"  */
 #define MS_MASK_TAINT_TOLERATION (1u << 2)   /* "TaintToleration"   */
+#define MS_MASK_NODE_AFFINITY (1u << 3)      /* "NodeAffinity"      */
 
 #define MS_MAX_ORDINAL 0xFFFFDu /* (keys 0 and 1 are reserved: no feasible node) */
 
@@ -432,11 +434,58 @@ int ms_nam_term_sets_ext(ms_ctx *ctx, uint32_t n_sets, const ms_nam_term_set_ext
  *      the pods' FINAL scores: its nodes' raw scores through the rescales of
  *      every later node of the cluster, the first non-zero node of the cluster
  *      at 100. The element-wise uint64 MAX over the shards is selectHost over
- *      the cluster; ms_decode_device (flags NULL) turns it into results. */
+ *      the cluster; ms_decode_device turns it into results (flags NULL, or
+ *      ms_nam_flags_device's once a required set is registered, below). */
 #define MS_NAM_SEG_BYTES 104u
 int ms_nam_segment_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev, void *seg_dev, void *stream);
 int ms_nam_keys_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev, uint32_t n_shards,
                        uint32_t shard_index, const void *segs_all_dev, unsigned long long *keys_dev, void *stream);
+
+/* ---- MS_PLUGINS_NU_NN_NAM: NodeAffinity as a Filter plugin ------------------
+ * spec.nodeSelector and requiredDuringSchedulingIgnoredDuringExecution
+ * (k8s@v1.22.0 component-helpers nodeaffinity GetRequiredNodeAffinity /
+ * RequiredNodeAffinity.Match and plugins/nodeaffinity Filter, restated). A node
+ * passes when every nodeSelector pair equals its label AND, if the pod has a
+ * required node selector, at least one nodeSelectorTerm matches (all its
+ * matchExpressions hold; a term without expressions and a selector without terms
+ * match nothing). Filter order is NodeUnschedulable, then NodeAffinity, the first
+ * failure wins per node: a FitError's mask holds MS_MASK_NODE_AFFINITY iff some
+ * present node passed NodeUnschedulable and failed NodeAffinity, and
+ * MS_MASK_NODE_UNSCHEDULABLE iff some present node failed NodeUnschedulable.
+ * Score, the in-loop hook and selectHost run over the feasible nodes only.
+ *
+ * A required set is the OR of n_terms terms, each the AND of two value-id sets
+ * (the form of ms_pref_term_ext.mask: a term matches a node whose zone id is in
+ * mask[0] and whose label2 id is in mask[1]). The shim folds the nodeSelector
+ * into every term's masks (a pod with only a nodeSelector has one term) and gives
+ * an empty term zero masks; matchFields and other label keys cannot be expressed
+ * and must be refused by the shim. n_terms = 0: no requirement.
+ * A pod's set id (pref_zone | pref_weight << 8) names BOTH tables: id s in
+ * 1..n_sets uses sets[s - 1]; id 0 and ids above n_sets have no requirement. The
+ * required and the preferred table are installed independently (replacing one
+ * keeps the other; n_sets = 0 clears); a value-id table that grows means both are
+ * re-registered. n_terms > MS_NAM_REQ_TERMS returns MS_E_INVAL. Synchronises like
+ * ms_nam_term_sets. Additive to ABI 7 (MS_ABI_VERSION unchanged): a caller
+ * detects the feature by the symbol ms_nam_required_sets.
+ *
+ * Node shards: ms_nam_segment_device's records also carry the two filter bits of
+ * the shard. ms_nam_flags_device ORs them per pod over the gathered shards
+ * (segs_all[s][p], as ms_nam_keys_device takes them) into flags_dev[p] (byte 0:
+ * NodeUnschedulable, byte 2: NodeAffinity), the word ms_decode_device takes as
+ * flags. With no required set registered, flags = NULL stays valid and exact;
+ * once one is registered the decode needs the flags (without them a FitError
+ * caused by NodeAffinity reads as NodeUnschedulable). */
+#define MS_NAM_REQ_TERMS 4
+typedef struct ms_req_term {
+    uint32_t mask[2][8];
+} ms_req_term; /* 64 bytes */
+typedef struct ms_nam_required_set {
+    ms_req_term term[MS_NAM_REQ_TERMS];
+    uint8_t n_terms, _pad[3];
+} ms_nam_required_set; /* 260 bytes */
+int ms_nam_required_sets(ms_ctx *ctx, uint32_t n_sets, const ms_nam_required_set *sets);
+int ms_nam_flags_device(ms_ctx *ctx, uint32_t n_pods, uint32_t n_shards, const void *segs_all_dev, uint32_t *flags_dev,
+                        void *stream);
 
 /* Whole exact sequential cycle on device-resident pods (single shard; on a
  * context joined to a communicator, the node-sharded cycle below). */

@@ -1,6 +1,6 @@
-// ms_affinity.hip — plugin set MS_PLUGINS_NU_NN_NAM: Filter[NodeUnschedulable];
-// Score[NodeNumber, NodeAffinity with several preferred terms], NodeAffinity's
-// ScoreExtensions = DefaultNormalizeScore(MaxNodeScore, reverse=false)
+// ms_affinity.hip — plugin set MS_PLUGINS_NU_NN_NAM: Filter[NodeUnschedulable,
+// NodeAffinity]; Score[NodeNumber, NodeAffinity with several preferred terms],
+// NodeAffinity's ScoreExtensions = DefaultNormalizeScore(MaxNodeScore, reverse=false)
 // (k8s@v1.22.0 plugins/nodeaffinity/node_affinity.go, helper/normalize_score.go;
 // restated) run by RunScorePlugins' in-loop hook exactly as written
 // (/root/reference/minisched/minisched.go:164-185).
@@ -44,6 +44,16 @@
 // each set into a lookup table (NamTab: per value id a 4-bit "these terms' sets
 // hold it" mask per key, and the weight sum of every 4-bit term mask), so a
 // row's raw score is wsum[z[zone] & l[label2]] for any operators.
+//
+// NodeAffinity as a Filter (nodeSelector and required terms,
+// ms_nam_required_sets): the same id names a pod's required set, so a class
+// still sees one feasible list. Required term k sits in bit 4 + k of the same
+// table bytes: the row passes when (z[zone] & l[label2]) >> 4 is non-zero, from
+// the lookup the raw score already makes. A row that fails is infeasible like an
+// unschedulable one, so the anchor, the rescales and F follow the shrunken list
+// with no other change. k_nam_seg also records per (segment, class) which
+// filter rejected a present row; k_nam_pick hands those bits to the decode per
+// pod, and over node shards they ride in the rescale records (k_nam_flags).
 #include <algorithm>
 
 #include "ms_device.h"
@@ -65,6 +75,8 @@ constexpr uint32_t kNamPickParts = 4;    // row parts per pod in a k_nam_pick wo
 struct NamSeg {
     uint8_t T[101];  // the composed rescale map on 0..100
     uint8_t any;     // a feasible node of the segment has a non-zero raw score
+    // the segment's filter bits (the FitError mask): [0] a present row failed
+    // NodeUnschedulable, [1] a present row passed it and failed NodeAffinity
     uint8_t _pad[2];
 };
 static_assert(sizeof(NamSeg) == MS_NAM_SEG_BYTES && kNamSegBytes == MS_NAM_SEG_BYTES, "NamSeg layout");
@@ -79,13 +91,27 @@ __device__ __forceinline__ uint32_t nam_row_word(const NodeTable &t, uint32_t r)
            ((uint32_t)t.label2[r] << 16) | ((d <= 9u ? d : 15u) << 24);
 }
 
-__device__ __forceinline__ bool nam_feasible(uint32_t w, uint32_t tol) { return (w & (tol ? 1u : 3u)) == 0u; }
+// The row-word bits that rule a row out for a class under NodeUnschedulable:
+// absent, and unschedulable unless the class tolerates it.
+__device__ __forceinline__ uint32_t nam_nu_bits(uint32_t tol) { return tol ? 1u : 3u; }
 
-// NodeAffinity.Score of a row word under a term table in LDS.
-__device__ __forceinline__ uint32_t nam_raw(uint32_t w, const uint8_t *tab) {
-    const uint32_t m = tab[(w >> 8) & 0xFFu] & tab[256u + ((w >> 16) & 0xFFu)];
+// NodeAffinity of a row word under a term table in LDS, one lookup for Score and
+// Filter: the terms whose two id sets hold the row's zone and label2 ids, bits 0-3
+// the preferred terms, bits 4-7 the required ones (a set without a requirement
+// has bit 4 on every value id; a lane without a class has an all-zero table).
+__device__ __forceinline__ uint32_t nam_terms(uint32_t w, const uint8_t *tab) {
+    return tab[(w >> 8) & 0xFFu] & tab[256u + ((w >> 16) & 0xFFu)];
+}
+// NodeAffinity.Score: the weight sum of the matching preferred terms.
+__device__ __forceinline__ uint32_t nam_raw(uint32_t m, const uint8_t *tab) {
     return reinterpret_cast<const uint16_t *>(tab + 512)[m & 15u];
 }
+// Both filters in one compare: feasible = no NodeUnschedulable bit of the row
+// under nu (nam_nu_bits) and a required term matched (m > 15). m < 256, so any
+// bit of w & nu lifts the bound past it. The key orders the rows the same way:
+// below 16 exactly for a row that passes NodeUnschedulable and fails NodeAffinity.
+__device__ __forceinline__ uint32_t nam_filter_key(uint32_t w, uint32_t nu, uint32_t m) { return ((w & nu) << 8) | m; }
+__device__ __forceinline__ bool nam_feasible(uint32_t w, uint32_t nu, uint32_t m) { return m > (((w & nu) << 8) | 15u); }
 
 // Class key (term set, toleration) of a pod: set ids past n_sets count as no terms.
 __device__ __forceinline__ uint32_t nam_key(const ms_pod_rec &p, uint32_t n_sets) {
@@ -241,16 +267,24 @@ __global__ void k_nam_rep(const uint32_t *__restrict__ ctl, const uint32_t *__re
 
 // A lane's class: its key's term table into the lane's LDS slot (kNamTabStride
 // apart: an odd word stride, so the per-lane lookups spread over the banks); all
-// 34 16-B loads issued before the stores. No terms: an all-zero table (raw 0).
+// 34 16-B loads issued before the stores. No set: no preferred term (raw 0) and
+// no requirement (bit 4 on every value id of both keys, as the host writes it
+// for a registered set without one). A lane without a class (!live) gets an
+// all-zero table: no required term ever matches, so none of its rows is feasible
+// and the row loops need no test of live.
 __device__ __forceinline__ void load_class_tab(uint8_t *tabs, const NamTab *__restrict__ sets,
                                                const uint32_t *__restrict__ cls_key, uint32_t c, bool live,
                                                uint32_t lane) {
-    constexpr uint32_t kVec = sizeof(NamTab) / 16;
+    constexpr uint32_t kVec = sizeof(NamTab) / 16, kIdVec = 512 / 16;  // (z and l: the first 512 bytes)
+    constexpr uint32_t kNoReq = kNamNoReqBit * 0x01010101u;
     const uint32_t sid = live ? cls_key[c] >> 1 : 0u;
     const uint4 *src = reinterpret_cast<const uint4 *>(sets + (sid ? sid - 1u : 0u));
     uint4 v[kVec];
 #pragma unroll
-    for (uint32_t k = 0; k < kVec; ++k) v[k] = sid ? src[k] : make_uint4(0, 0, 0, 0);
+    for (uint32_t k = 0; k < kVec; ++k) {
+        const uint32_t none = (live && k < kIdVec) ? kNoReq : 0u;
+        v[k] = sid ? src[k] : make_uint4(none, none, none, none);
+    }
     uint32_t *dst = reinterpret_cast<uint32_t *>(tabs + lane * kNamTabStride);
 #pragma unroll
     for (uint32_t k = 0; k < kVec; ++k) {
@@ -278,11 +312,21 @@ __global__ __launch_bounds__(64) void k_nam_seg(NodeTable t, uint32_t n_rows, ui
     const bool live = c < n_cls;
     load_class_tab(terms, sets, cls_key, c, live, lane);
     const uint8_t *tb = terms + lane * kNamTabStride;
-    const uint32_t tol = live ? (cls_key[c] & 1u) : 0u;
+    const uint32_t tol = live ? (cls_key[c] & 1u) : 0u, nu = nam_nu_bits(tol);
     const uint32_t r0 = blockIdx.y * seg_rows, r1 = min(n_rows, r0 + seg_rows);
     uint8_t *mine = tabs + lane * kNamStride;
     table_identity(mine);
     uint32_t any = 0, top = 100;  // top = T(100): 0 once the table is all 0
+    // the filter bits: a present row failed NodeUnschedulable / passed it and failed
+    // NodeAffinity. The decode reads them only for a pod with no feasible node
+    // anywhere, so they need to be exact only for such a class: the early exit
+    // below fires only after a feasible (non-zero) row, and rows it skips are
+    // then never missed. Whether a present row is unschedulable does not depend on
+    // the class: it is noted while the rows are staged (unsched, the lane's own
+    // rows; the wave's OR at the end), so the row loop carries NodeAffinity's bit
+    // alone: the least nam_filter_key, below 16 once such a row was seen.
+    bool unsched = false;
+    uint32_t na_min = 0xFFFFFFFFu;
     for (uint32_t base = r0; base < r1; base += kNamTile) {
         const uint32_t nt = min(kNamTile, r1 - base);
         // a lane is done once its table is all 0 and it has seen a non-zero node
@@ -290,7 +334,11 @@ __global__ __launch_bounds__(64) void k_nam_seg(NodeTable t, uint32_t n_rows, ui
         if (__ballot(!done) == 0) break;  // (one wave: wave-uniform)
         const uint32_t nt4 = (nt + 3u) & ~3u;  // (rows past nt: absent, never feasible)
         __builtin_amdgcn_wave_barrier();
-        for (uint32_t i = lane; i < nt4; i += 64u) tile[i] = i < nt ? nam_row_word(t, base + i) : 1u;
+        for (uint32_t i = lane; i < nt4; i += 64u) {
+            const uint32_t w = i < nt ? nam_row_word(t, base + i) : 1u;
+            tile[i] = w;
+            unsched = unsched || (w & 3u) == 2u;
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // four rows per step: when no lane rescales at any of them (one ballot)
@@ -302,8 +350,10 @@ __global__ __launch_bounds__(64) void k_nam_seg(NodeTable t, uint32_t n_rows, ui
             bool fv[4], resc = false;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                fv[k] = live && nam_feasible(wv[k], tol);
-                rv[k] = nam_raw(wv[k], tb);
+                const uint32_t m = nam_terms(wv[k], tb);
+                rv[k] = nam_raw(m, tb);
+                fv[k] = nam_feasible(wv[k], nu, m);
+                na_min = min(na_min, nam_filter_key(wv[k], nu, m));
                 any |= (fv[k] && rv[k] > 0u) ? 1u : 0u;
                 resc = resc || (fv[k] && rv[k] > 100u);
             }
@@ -323,9 +373,11 @@ __global__ __launch_bounds__(64) void k_nam_seg(NodeTable t, uint32_t n_rows, ui
             }
         }
     }
+    const bool nu_fail = __ballot(unsched) != 0 && !tol;  // (before any lane leaves)
     if (!live) return;
     mine[101] = (uint8_t)any;
-    mine[102] = mine[103] = 0;
+    mine[102] = nu_fail ? 1 : 0;
+    mine[103] = na_min < 16u ? 1 : 0;
     const uint32_t *src = reinterpret_cast<const uint32_t *>(mine);
     uint32_t *dst = reinterpret_cast<uint32_t *>(out + (size_t)blockIdx.y * stride + c);
 #pragma unroll
@@ -333,9 +385,10 @@ __global__ __launch_bounds__(64) void k_nam_seg(NodeTable t, uint32_t n_rows, ui
 }
 
 // Per lane p < n_lanes: out = the composition of n records in order (in[s * stride + p], s
-// ascending: out.T = T_{n-1} o .. o T_0) and the OR of their "any". With skip_to:
-// only the records s > skip_to (a shard's suffix), and m_in gets the OR of the
-// records s < skip_to. n_live (optional): lanes past *n_live skip.
+// ascending: out.T = T_{n-1} o .. o T_0), the OR of their "any" and the OR of their
+// filter bits. With skip_to: only the records s > skip_to (a shard's suffix), and
+// m_in gets the OR of "any" of the records s < skip_to; the filter bits stay the
+// OR over all n records. n_live (optional): lanes past *n_live skip.
 __global__ void k_nam_compose(const NamSeg *__restrict__ in, uint32_t stride, uint32_t n, uint32_t n_lanes,
                               int32_t skip_to, NamSeg *__restrict__ out, uint8_t *__restrict__ m_in,
                               const uint32_t *__restrict__ n_live) {
@@ -346,9 +399,12 @@ __global__ void k_nam_compose(const NamSeg *__restrict__ in, uint32_t stride, ui
     uint8_t *U = tabs + threadIdx.x * kNamStride;  // (LDS, not a dynamically indexed private array)
     uint8_t *st = stg + threadIdx.x * kNamStride;  // the record being composed, staged as words
     table_identity(U);
-    uint32_t any = 0, before = 0;
+    uint32_t any = 0, before = 0, nu_fail = 0, na_fail = 0;
     for (uint32_t s = 0; s < n; ++s) {
         const NamSeg *x = in + (size_t)s * stride + p;
+        // (the filter bits are cluster-wide: the OR over ALL records, skipped ones too)
+        nu_fail |= x->_pad[0];
+        na_fail |= x->_pad[1];
         if (skip_to >= 0 && (int32_t)s < skip_to) {
             before |= x->any;
             continue;
@@ -364,7 +420,8 @@ __global__ void k_nam_compose(const NamSeg *__restrict__ in, uint32_t stride, ui
         for (uint32_t v = 0; v <= 100u; ++v) U[v] = st[U[v]];
     }
     U[101] = (uint8_t)any;
-    U[102] = U[103] = 0;
+    U[102] = (uint8_t)nu_fail;
+    U[103] = (uint8_t)na_fail;
     const uint32_t *src = reinterpret_cast<const uint32_t *>(U);
     uint32_t *dst = reinterpret_cast<uint32_t *>(out + p);
 #pragma unroll
@@ -389,6 +446,24 @@ __global__ void k_nam_expand(const NamSeg *__restrict__ cls_rec, const uint32_t 
     if (i >= n * kW) return;
     const uint32_t p = i / kW, w = i % kW;
     reinterpret_cast<uint32_t *>(out + p)[w] = reinterpret_cast<const uint32_t *>(cls_rec + pcls[p])[w];
+}
+
+// The decode's filter word (byte 0: NodeUnschedulable, byte 2: NodeAffinity;
+// decode_key) from the filter bits of n records x[s * stride], ORed.
+__device__ __forceinline__ uint32_t nam_filter_word(const NamSeg *__restrict__ x, uint32_t stride, uint32_t n) {
+    uint32_t nu_fail = 0, na_fail = 0;
+    for (uint32_t s = 0; s < n; ++s) {
+        nu_fail |= x[(size_t)s * stride]._pad[0];
+        na_fail |= x[(size_t)s * stride]._pad[1];
+    }
+    return (nu_fail ? 1u : 0u) | (na_fail ? 0x10000u : 0u);
+}
+
+// Node shards: per pod that word over the n gathered records in[s * stride + p].
+__global__ void k_nam_flags(const NamSeg *__restrict__ in, uint32_t stride, uint32_t n, uint32_t n_pods,
+                            uint32_t *__restrict__ flags) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n_pods) flags[p] = nam_filter_word(in + p, stride, n);
 }
 
 // Node name digit of a row word (0..9; 10 = none).
@@ -422,7 +497,7 @@ __global__ __launch_bounds__(64) void k_nam_fscore(NodeTable t, uint32_t n_rows,
     const bool live = c < n_cls;
     load_class_tab(terms, sets, cls_key, c, live, lane);
     const uint8_t *tb = terms + lane * kNamTabStride;
-    const uint32_t tol = live ? (cls_key[c] & 1u) : 0u;
+    const uint32_t nu = nam_nu_bits(live ? (cls_key[c] & 1u) : 0u);
     for (uint32_t d = 0; d < 12u; ++d) fm[lane][d] = 0u;
     // T_{>segment}: the later segments' tables, then the later shards'
     uint8_t *mine = tabs + lane * kNamStride;
@@ -471,8 +546,9 @@ __global__ __launch_bounds__(64) void k_nam_fscore(NodeTable t, uint32_t n_rows,
             bool fv[4], resc = false;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                fv[k] = live && nam_feasible(wv[k], tol);
-                rv[k] = nam_raw(wv[k], tb);
+                const uint32_t m = nam_terms(wv[k], tb);
+                rv[k] = nam_raw(m, tb);
+                fv[k] = nam_feasible(wv[k], nu, m);
                 resc = resc || (fv[k] && rv[k] > 100u);
             }
             const bool fix = __ballot(resc && top != 0u) == 0;  // (wave-uniform) the table is fixed across the four
@@ -532,13 +608,15 @@ __device__ __forceinline__ uint32_t zero_bytes(uint32_t y) {
 // Workgroup = 64 pods x kNamPickParts waves (wave w: row part w of the
 // workgroup's grid.y slice), combined in LDS, then one atomicMax per pod into
 // keys[p] (filled before with kKeyListed / 0: this context lists rows but none is
-// feasible / lists none). grid.y x kNamPickParts parts keep many waves in flight
+// feasible / lists none); the first row slice also writes the pod's filter word
+// for the decode. grid.y x kNamPickParts parts keep many waves in flight
 // over the row stream (lane = pod alone gives one wave per 64 pods).
 __global__ __launch_bounds__(64 * kNamPickParts) void k_nam_pick(
     const ms_pod_rec *__restrict__ pods, uint32_t n_pods, const uint32_t *__restrict__ perm,
     const uint32_t *__restrict__ pcls, const uint8_t *__restrict__ F, uint32_t fpitch,
     const uint32_t *__restrict__ fmax, const uint8_t *__restrict__ dmask, uint32_t n_rows, uint32_t rows_per_part,
-    uint32_t base, uint32_t seed32, uint32_t w_nn, uint32_t w_na, u64 *__restrict__ keys) {
+    uint32_t base, uint32_t seed32, uint32_t w_nn, uint32_t w_na, u64 *__restrict__ keys,
+    const NamSeg *__restrict__ local, uint32_t stride, uint32_t n_segs, uint32_t *__restrict__ flags) {
     __shared__ u64 part_best[kNamPickParts][64];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     const uint32_t i = blockIdx.x * 64u + lane;
@@ -601,6 +679,10 @@ __global__ __launch_bounds__(64 * kNamPickParts) void k_nam_pick(
 #pragma unroll
         for (uint32_t w = 1; w < kNamPickParts; ++w) b = umax64(b, part_best[w][lane]);
         if (b) atomicMax(reinterpret_cast<unsigned long long *>(keys + p), (unsigned long long)b);
+        // one context (flags): the pod's filter word, the OR over the row segments of its
+        // class (local: k_nam_seg's records). The decode reads it only for a pod without a
+        // feasible row, so only a class without one (fall == 0) walks its records.
+        if (flags && blockIdx.y == 0) flags[p] = fall ? 0u : nam_filter_word(local + c, stride, n_segs);
     }
 }
 
@@ -703,10 +785,18 @@ hipError_t launch_nam_compose(const void *in, uint32_t stride, uint32_t n, uint3
     return hipGetLastError();
 }
 
+hipError_t launch_nam_flags(const void *in, uint32_t stride, uint32_t n, uint32_t n_pods, uint32_t *flags,
+                            hipStream_t s) {
+    if (n_pods == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_nam_flags, dim3(cdiv(n_pods, 256u)), dim3(256), 0, s, static_cast<const NamSeg *>(in), stride,
+                       n, n_pods, flags);
+    return hipGetLastError();
+}
+
 hipError_t launch_nam_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
                            const void *sets, uint32_t n_sets, uint32_t seed32, uint32_t w_nn, uint32_t w_na,
                            const void *after, const uint8_t *m_in, uint32_t listed, const NamLayout &L,
-                           void *scratch, unsigned long long *keys, hipStream_t s) {
+                           void *scratch, unsigned long long *keys, uint32_t *flags, hipStream_t s) {
     if (n_pods == 0) return hipSuccess;
     if (!nam_launch_ok(L, n_pods, n_sets)) return hipErrorInvalidValue;
     const NamScratch x = nam_carve(scratch, L, n_pods, n_sets);
@@ -734,7 +824,7 @@ hipError_t launch_nam_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec
     hipLaunchKernelGGL(k_nam_pick, dim3(pod_blocks, gy), dim3(64 * kNamPickParts), 0, s, pods, n_pods,
                        (const uint32_t *)x.perm, (const uint32_t *)x.pcls, (const uint8_t *)x.F, L.fpitch,
                        (const uint32_t *)x.fmax, (const uint8_t *)x.dmask, n_rows, rows_per_part, t.base, seed32, w_nn,
-                       w_na, reinterpret_cast<u64 *>(keys));
+                       w_na, reinterpret_cast<u64 *>(keys), (const NamSeg *)x.local, L.cls_max, L.segs, flags);
     return hipGetLastError();
 }
 

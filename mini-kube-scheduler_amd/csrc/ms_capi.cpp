@@ -425,20 +425,23 @@ int ensure_nam(ms_ctx *c, const NamPlan &plan) {
 // This shard's packed keys of a chunk of nb pods into keys, carved with the
 // call's layout L (the one ensure_nam sized the scratch for): per class its
 // rows' normalised scores under the later segments' and (after / m_in, node
-// shards) the later shards' rescales, then per pod the best key.
+// shards) the later shards' rescales, then per pod the best key. flags
+// (optional): per pod which filters rejected a present row of this context, the
+// word the decode takes (no rows: zero).
 int nam_keys_locked(ms_ctx *c, const NamLayout &L, uint32_t nb, const ms_pod_rec *d_pods, const void *after,
-                    const uint8_t *m_in, unsigned long long *keys, hipStream_t s) {
+                    const uint8_t *m_in, unsigned long long *keys, uint32_t *flags, hipStream_t s) {
     if (c->rows_dev == 0) {
         MS_HIP(c, launch_fill_keys(keys, nb, 0ull, s));
+        if (flags) MS_HIP(c, hipMemsetAsync(flags, 0, sizeof(uint32_t) * nb, s));
         return MS_OK;
     }
     MS_HIP(c, launch_nam_keys(c->t, c->rows_dev, d_pods, nb, c->d_terms, c->n_terms, seed32_of(c->cfg.seed), c->w_nn,
-                              c->w_na, after, m_in, c->present_dev ? 1u : 0u, L, c->d_nam, keys, s));
+                              c->w_na, after, m_in, c->present_dev ? 1u : 0u, L, c->d_nam, keys, flags, s));
     return MS_OK;
 }
 
-// The single-shard NAM cycle: keys per chunk, decode, and with commit each
-// winner's NodeInfo.AddPod (stateless: no later pod reads it).
+// The single-shard NAM cycle: keys and filter flags per chunk, decode, and with
+// commit each winner's NodeInfo.AddPod (stateless: no later pod reads it).
 int nam_cycle_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_result *d_res, int commit,
                      hipStream_t s) {
     const NamPlan plan = nam_plan_for(c, n_pods);
@@ -447,9 +450,9 @@ int nam_cycle_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_re
     if (rc) return rc;
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
-        rc = nam_keys_locked(c, plan.L, nb, d_pods + s0, nullptr, nullptr, c->d_keys, s);
+        rc = nam_keys_locked(c, plan.L, nb, d_pods + s0, nullptr, nullptr, c->d_keys, c->d_flags, s);
         if (rc) return rc;
-        MS_HIP(c, launch_decode(d_pods + s0, nb, c->d_keys, nullptr, c->present_dev, d_res + s0, s));
+        MS_HIP(c, launch_decode(d_pods + s0, nb, c->d_keys, c->d_flags, c->present_dev, d_res + s0, s));
         if (commit) MS_HIP(c, launch_apply_binds(c->t, d_pods + s0, nb, d_res + s0, s));
     }
     return MS_OK;
@@ -1406,22 +1409,37 @@ int ms_tt_final_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, u
     return tt2_shard_epilogue(c, s);
 }
 
-// A term set in general form -> the device's lookup table (NamTab).
-static NamTab nam_tab_of(const ms_nam_term_set_ext &x) {
+// Set id's lookup table (NamTab) from its preferred term set and its required
+// set (either may be null: the id is past that table). Preferred term k: bit k of
+// z[v] / l[v]; required term k: bit 4 + k; no requirement: kNamNoReqBit on every
+// value id of both keys (every node passes).
+static NamTab nam_tab_of(const ms_nam_term_set_ext *x, const ms_nam_required_set *q) {
     NamTab t{};
-    for (int k = 0; k < MS_NAM_TERMS; ++k) {
-        const ms_pref_term_ext &e = x.term[k];
+    auto holds = [](const uint32_t *mask, uint32_t v) { return (mask[v >> 5] >> (v & 31u)) & 1u; };
+    for (int k = 0; x && k < MS_NAM_TERMS; ++k) {
+        const ms_pref_term_ext &e = x->term[k];
         if (e.weight == 0) continue;
         for (uint32_t v = 0; v < 256u; ++v) {
-            if ((e.mask[0][v >> 5] >> (v & 31u)) & 1u) t.z[v] |= (uint8_t)(1u << k);
-            if ((e.mask[1][v >> 5] >> (v & 31u)) & 1u) t.l[v] |= (uint8_t)(1u << k);
+            if (holds(e.mask[0], v)) t.z[v] |= (uint8_t)(1u << k);
+            if (holds(e.mask[1], v)) t.l[v] |= (uint8_t)(1u << k);
         }
     }
     for (uint32_t m = 0; m < 16u; ++m) {
         uint32_t w = 0;
-        for (int k = 0; k < MS_NAM_TERMS; ++k)
-            if ((m >> k) & 1u) w += x.term[k].weight;
+        for (int k = 0; x && k < MS_NAM_TERMS; ++k)
+            if ((m >> k) & 1u) w += x->term[k].weight;
         t.wsum[m] = (uint16_t)w;
+    }
+    const uint32_t n_req = q ? q->n_terms : 0u;
+    for (uint32_t v = 0; v < 256u; ++v) {
+        if (n_req == 0) {
+            t.z[v] |= (uint8_t)kNamNoReqBit;
+            t.l[v] |= (uint8_t)kNamNoReqBit;
+        }
+        for (uint32_t k = 0; k < n_req; ++k) {
+            if (holds(q->term[k].mask[0], v)) t.z[v] |= (uint8_t)(kNamNoReqBit << k);
+            if (holds(q->term[k].mask[1], v)) t.l[v] |= (uint8_t)(kNamNoReqBit << k);
+        }
     }
     return t;
 }
@@ -1447,9 +1465,19 @@ static ms_nam_term_set_ext nam_ext_of(const ms_nam_term_set &x) {
     return e;
 }
 
-static int nam_install(ms_ctx *c, const std::vector<NamTab> &tabs, const char *who) {
-    const uint32_t n_sets = (uint32_t)tabs.size();
+// Installs the context's tables after one of them was replaced (pref / req: the
+// new one, or null to keep the registered one): a NamTab for each of
+// max(preferred sets, required sets) ids, built from the host copies of both.
+static int nam_install(ms_ctx *c, std::vector<ms_nam_term_set_ext> *pref, std::vector<ms_nam_required_set> *req,
+                       const char *who) {
     std::lock_guard<std::mutex> g(c->sched_mu);
+    if (pref) c->h_pref.swap(*pref);
+    if (req) c->h_req.swap(*req);
+    const uint32_t n_pref = (uint32_t)c->h_pref.size(), n_req = (uint32_t)c->h_req.size();
+    const uint32_t n_sets = std::max(n_pref, n_req);
+    std::vector<NamTab> tabs(n_sets);
+    for (uint32_t i = 0; i < n_sets; ++i)
+        tabs[i] = nam_tab_of(i < n_pref ? &c->h_pref[i] : nullptr, i < n_req ? &c->h_req[i] : nullptr);
     MS_HIP(c, hipSetDevice(c->cfg.device));
     MS_HIP(c, hipDeviceSynchronize());  // (no cycle still reads the previous table; a configuration call)
     if (n_sets > c->terms_cap) {
@@ -1467,7 +1495,7 @@ int ms_nam_term_sets(ms_ctx *c, uint32_t n_sets, const ms_nam_term_set *sets) {
     if (!valid_ctx(c) || (n_sets && !sets) || n_sets > 0xFFFFu) return MS_E_INVAL;
     if (c->cfg.plugin_set != MS_PLUGINS_NU_NN_NAM)
         return fail(c, MS_E_INVAL, "ms_nam_term_sets: the multi-term NodeAffinity plugin set only");
-    std::vector<NamTab> tabs(n_sets);
+    std::vector<ms_nam_term_set_ext> pref(n_sets);
     for (uint32_t i = 0; i < n_sets; ++i) {
         for (int k = 0; k < MS_NAM_TERMS; ++k) {
             const ms_pref_term &x = sets[i].term[k];
@@ -1476,22 +1504,31 @@ int ms_nam_term_sets(ms_ctx *c, uint32_t n_sets, const ms_nam_term_set *sets) {
             // (value 0xFF is Exists; an In term names a value id 1..254, so a node label id
             // of 255 matches Exists only: ZoneIds hands out at most 254 ids)
         }
-        tabs[i] = nam_tab_of(nam_ext_of(sets[i]));
+        pref[i] = nam_ext_of(sets[i]);
     }
-    return nam_install(c, tabs, "ms_nam_term_sets");
+    return nam_install(c, &pref, nullptr, "ms_nam_term_sets");
 }
 
 int ms_nam_term_sets_ext(ms_ctx *c, uint32_t n_sets, const ms_nam_term_set_ext *sets) {
     if (!valid_ctx(c) || (n_sets && !sets) || n_sets > 0xFFFFu) return MS_E_INVAL;
     if (c->cfg.plugin_set != MS_PLUGINS_NU_NN_NAM)
         return fail(c, MS_E_INVAL, "ms_nam_term_sets_ext: the multi-term NodeAffinity plugin set only");
-    std::vector<NamTab> tabs(n_sets);
-    for (uint32_t i = 0; i < n_sets; ++i) {
+    for (uint32_t i = 0; i < n_sets; ++i)
         for (int k = 0; k < MS_NAM_TERMS; ++k)
             if (sets[i].term[k].weight > 100) return fail(c, MS_E_INVAL, "ms_nam_term_sets_ext: weight 0..100");
-        tabs[i] = nam_tab_of(sets[i]);
-    }
-    return nam_install(c, tabs, "ms_nam_term_sets_ext");
+    std::vector<ms_nam_term_set_ext> pref(sets, sets + n_sets);
+    return nam_install(c, &pref, nullptr, "ms_nam_term_sets_ext");
+}
+
+int ms_nam_required_sets(ms_ctx *c, uint32_t n_sets, const ms_nam_required_set *sets) {
+    if (!valid_ctx(c) || (n_sets && !sets) || n_sets > 0xFFFFu) return MS_E_INVAL;
+    if (c->cfg.plugin_set != MS_PLUGINS_NU_NN_NAM)
+        return fail(c, MS_E_INVAL, "ms_nam_required_sets: the multi-term NodeAffinity plugin set only");
+    for (uint32_t i = 0; i < n_sets; ++i)
+        if (sets[i].n_terms > MS_NAM_REQ_TERMS)
+            return fail(c, MS_E_INVAL, "ms_nam_required_sets: at most MS_NAM_REQ_TERMS terms per set");
+    std::vector<ms_nam_required_set> req(sets, sets + n_sets);
+    return nam_install(c, nullptr, &req, "ms_nam_required_sets");
 }
 
 int ms_nam_segment_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, void *seg_dev, void *stream) {
@@ -1550,10 +1587,24 @@ int ms_nam_keys_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, u
         // the later shards' tables composed, and whether an earlier shard has a non-zero node
         MS_HIP(c, launch_nam_compose(static_cast<const char *>(segs_all_dev) + (size_t)s0 * MS_NAM_SEG_BYTES, n_pods,
                                      n_shards, nb, (int32_t)shard_index, after, m_in, s));
-        rc = nam_keys_locked(c, plan.L, nb, pods_dev + s0, after, m_in, keys_dev + s0, s);
+        rc = nam_keys_locked(c, plan.L, nb, pods_dev + s0, after, m_in, keys_dev + s0, nullptr, s);
         if (rc) return rc;
     }
     return chain_back(c, s);
+}
+
+int ms_nam_flags_device(ms_ctx *c, uint32_t n_pods, uint32_t n_shards, const void *segs_all_dev, uint32_t *flags_dev,
+                        void *stream) {
+    if (!valid_ctx(c) || (n_pods && (!segs_all_dev || !flags_dev))) return MS_E_INVAL;
+    if (c->cfg.plugin_set != MS_PLUGINS_NU_NN_NAM)
+        return fail(c, MS_E_INVAL, "ms_nam_flags_device: the multi-term NodeAffinity plugin set only");
+    if (n_shards == 0) return fail(c, MS_E_INVAL, "ms_nam_flags_device: no shards");
+    if (n_pods == 0) return MS_OK;
+    // (reads the caller's gathered records only: no table, no scratch, so no ordering
+    // against the context stream, like ms_decode_device)
+    MS_HIP(c, hipSetDevice(c->cfg.device));
+    MS_HIP(c, launch_nam_flags(segs_all_dev, n_pods, n_shards, n_pods, flags_dev, pick_stream(c, stream)));
+    return MS_OK;
 }
 
 }  // extern "C"

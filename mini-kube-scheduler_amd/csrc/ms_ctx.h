@@ -161,8 +161,13 @@ struct ms_ctx {
     hipStream_t tt_stream = nullptr;  // (not owned: the context's, a caller's or the communicator's)
     // MS_PLUGINS_NU_NN_NAM: the registered term sets as lookup tables (NamTab) and the
     // per-class passes' scratch of a chunk (nam_bytes allocated)
+    // n_terms counts the ids with a table: max(preferred sets, required sets). The
+    // host keeps both registered tables (h_pref, h_req), since each is replaced
+    // on its own and every id's NamTab holds its share of both.
     DevBuf<void> d_terms;
     uint32_t n_terms = 0, terms_cap = 0;
+    std::vector<ms_nam_term_set_ext> h_pref;
+    std::vector<ms_nam_required_set> h_req;
     DevBuf<void> d_nam;
     size_t nam_bytes = 0;
     // node-sharded sequential mode: merged candidate lists (ms_seq_validate_device)

@@ -108,8 +108,10 @@ __device__ __forceinline__ uint32_t first_slot(uint32_t m) {
 // Combined key -> per-pod outcome (minisched.go:143-148 FitError, :70-75 the
 // score-error path, :80 selectHost's node). Keys 0 and 1 carry no node: 1 =
 // some shard lists a node but none is feasible (kKeyListed), 0 = no shard
-// lists any. flags: per-pod filter bytes of the resource-aware set (byte 0 NU,
-// byte 1 NRF) or nullptr for NU+NN / NodeAffinity, where NodeUnschedulable is
+// lists any. flags: per-pod filter bytes (byte 0 NU, byte 1 NRF of the
+// resource-aware set, byte 2 NodeAffinity's Filter of the multi-term set: 1 =
+// the plugin rejected a present node) or nullptr for NU+NN / NodeAffinity
+// (multi-term: only while no required set is registered), where NodeUnschedulable is
 // the only filter: F = 0 with a node listed (key 1, or a non-zero present
 // count) means it rejected every node.
 __device__ __forceinline__ ms_result decode_key(u64 k, int8_t pod_digit, const uint32_t *flags, uint32_t i,
@@ -123,7 +125,8 @@ __device__ __forceinline__ ms_result decode_key(u64 k, int8_t pod_digit, const u
         if (flags) {
             const uint32_t f = flags[i];
             r.plugin_mask = ((f & 0xFFu) ? MS_MASK_NODE_UNSCHEDULABLE : 0u) |
-                            ((f & 0xFF00u) ? MS_MASK_NODE_RESOURCES_FIT : 0u);
+                            ((f & 0xFF00u) ? MS_MASK_NODE_RESOURCES_FIT : 0u) |
+                            ((f & 0xFF0000u) ? MS_MASK_NODE_AFFINITY : 0u);
         } else {
             // NU+NN: NodeUnschedulable is the only filter, so F == 0 with at
             // least one node listed means every node was rejected by it.

@@ -182,11 +182,16 @@ __host__ __device__ inline uint32_t tb_unhash(uint32_t A, uint32_t h) { return (
 // A term set as the device reads it (built on the host from ms_nam_term_set(_ext)):
 // z[v] / l[v] bit t = term t (weight > 0) holds zone / label2 value id v; wsum[m]
 // = the weight sum of the terms in 4-bit mask m. raw = wsum[z[zone] & l[label2]].
+// The high nibble is the id's required set (ms_nam_required_sets): bit 4 + k =
+// required term k holds the value id; a node passes NodeAffinity's Filter when
+// (z[zone] & l[label2]) >> 4 is non-zero. An id without a requirement has
+// kNamNoReqBit on every value id of both keys, so the device needs no flag.
 struct NamTab {
     uint8_t z[256];
     uint8_t l[256];
     uint16_t wsum[16];
 };
+constexpr uint32_t kNamNoReqBit = 0x10u;
 // NamLayout (row segments and scratch shape), the carve offsets and a call's
 // NamPlan: ms_nam_layout.h (host-only arithmetic). Every chunk of a call is
 // launched with the call's plan layout L, never one of its own pod count.
@@ -205,10 +210,16 @@ hipError_t launch_nam_compose(const void *in, uint32_t stride, uint32_t n, uint3
 // Per pod the best packed key over this context's rows (keys[p] written; listed:
 // the context lists a row, so a pod with none feasible gets kKeyListed); after /
 // m_in: launch_nam_compose's outputs for these pods (node shards), or null.
+// flags (optional): per pod this context's filter word for the decode (byte 0
+// NodeUnschedulable, byte 2 NodeAffinity rejected a present row).
 hipError_t launch_nam_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
                            const void *sets, uint32_t n_sets, uint32_t seed32, uint32_t w_nn, uint32_t w_na,
                            const void *after, const uint8_t *m_in, uint32_t listed, const NamLayout &L,
-                           void *scratch, unsigned long long *keys, hipStream_t s);
+                           void *scratch, unsigned long long *keys, uint32_t *flags, hipStream_t s);
+// Node shards: flags[p] = that word from the OR of the filter bits of the n
+// gathered records in[s * stride + p].
+hipError_t launch_nam_flags(const void *in, uint32_t stride, uint32_t n, uint32_t n_pods, uint32_t *flags,
+                            hipStream_t s);
 
 // ---- launchers (ms_kernels.hip) -------------------------------------------
 // All return hipError_t of the launch; none synchronises.

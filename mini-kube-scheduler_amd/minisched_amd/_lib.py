@@ -36,6 +36,7 @@ CODE_SUCCESS, CODE_ERROR, CODE_UNSCHEDULABLE = 0, 1, 2
 MASK_NODE_UNSCHEDULABLE = 1
 MASK_NODE_RESOURCES_FIT = 2
 MASK_TAINT_TOLERATION = 4
+MASK_NODE_AFFINITY = 8
 MAX_ORDINAL = 0xFFFFD  # keys 0 / 1 are reserved (no feasible node)
 
 ERRNAMES = {
@@ -151,6 +152,34 @@ def nam_term_sets_to_ext(sets16):
     return nam_term_sets_ext_array(sets)
 
 
+NAM_REQ_TERMS = 4  # MS_NAM_REQ_TERMS
+NAM_REQ_TERM_BYTES = 64  # ms_req_term
+NAM_REQ_SET_BYTES = 260  # ms_nam_required_set
+
+
+def nam_required_sets_array(sets):
+    """ms_nam_required_set records (uint8 (n, 260)) from a list of required sets:
+    None (no requirement) or the terms [(zone id set, label2 id set), ...] whose OR
+    a node must satisfy (1..MS_NAM_REQ_TERMS; id sets as in nam_term_sets_ext_array;
+    an empty term, which matches nothing, is (0, 0)). Set i is set id i + 1.
+    encode.NamTerms.required_sets builds them from nodeSelector and required terms
+    (a required selector without terms there becomes the one term (0, 0))."""
+    out = np.zeros((len(sets), NAM_REQ_SET_BYTES), dtype=np.uint8)
+    for i, terms in enumerate(sets):
+        if terms is None:
+            continue
+        if not 1 <= len(terms) <= NAM_REQ_TERMS:
+            raise ValueError(f"1..{NAM_REQ_TERMS} required terms per set (None: no requirement)")
+        for k, (zmask, lmask) in enumerate(terms):
+            if not 0 <= zmask <= _ALL_IDS or not 0 <= lmask <= _ALL_IDS:
+                raise ValueError("required term: id sets within 256 bits")
+            b = k * NAM_REQ_TERM_BYTES
+            out[i, b:b + 32] = np.frombuffer(int(zmask).to_bytes(32, "little"), dtype=np.uint8)
+            out[i, b + 32:b + 64] = np.frombuffer(int(lmask).to_bytes(32, "little"), dtype=np.uint8)
+        out[i, NAM_REQ_TERMS * NAM_REQ_TERM_BYTES] = len(terms)
+    return out
+
+
 def nam_term_sets_array(sets):
     """ms_nam_term_set records (uint8 (n, 16)) from a list of term lists
     [(label key 0|1, value id 1..254 or 0xFF for Exists, weight 1..100), ...]
@@ -258,6 +287,8 @@ SIGNATURES = {
     "ms_nam_term_sets_ext": (ctypes.c_int, [_vp, _u32, _vp]),
     "ms_nam_segment_device": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp]),
     "ms_nam_keys_device": (ctypes.c_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "ms_nam_required_sets": (ctypes.c_int, [_vp, _u32, _vp]),
+    "ms_nam_flags_device": (ctypes.c_int, [_vp, _u32, _u32, _vp, _vp, _vp]),
     "ms_comm_id_create": (ctypes.c_int, [ctypes.POINTER(ms_comm_id)]),
     "ms_comm_init": (ctypes.c_int, [_vp, ctypes.POINTER(ms_comm_id), _i32, _i32]),
     "ms_sharded_slice": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
@@ -547,6 +578,21 @@ class Engine:
         self._check("ms_nam_keys_device",
                     self.lib.ms_nam_keys_device(self.h, n_pods, pods_dev, n_shards, shard_index, segs_all_dev, keys_dev,
                                                 stream or None))
+
+    def nam_required_sets(self, sets):
+        """NodeAffinity as a filter (nodeSelector and required terms): uint8 (n, 260)
+        ms_nam_required_set records (nam_required_sets_array); a pod's set id names
+        its required set as it names its preferred one. Installed independently
+        of the preferred table; an empty array clears."""
+        raw = np.ascontiguousarray(np.asarray(sets, dtype=np.uint8).reshape(-1, NAM_REQ_SET_BYTES))
+        self._check("ms_nam_required_sets",
+                    self.lib.ms_nam_required_sets(self.h, len(raw), raw.ctypes.data if len(raw) else None))
+
+    def nam_flags_device(self, n_pods, n_shards, segs_all_dev, flags_dev, stream=0):
+        """Node shards: per pod the OR of the gathered records' filter bits, as the
+        flags decode_device takes (needed once a required set is registered)."""
+        self._check("ms_nam_flags_device",
+                    self.lib.ms_nam_flags_device(self.h, n_pods, n_shards, segs_all_dev, flags_dev, stream or None))
 
     # ---- in-library multi-GPU (a communicator per job) -------------------------
     def comm_init(self, comm_id: bytes, rank: int, world: int):

@@ -236,8 +236,10 @@ _INT64 = re.compile(r"^[+-]?[0-9]+$")
 
 
 class UnsupportedTerm(ValueError):
-    """A preferred term the device records cannot express (a requirement on a
-    label key other than the two encoded ones, more than MS_NAM_TERMS terms)."""
+    """A preferred or required term the device records cannot express (a
+    requirement or nodeSelector key other than the two encoded label keys,
+    matchFields, more than MS_NAM_TERMS preferred or MS_NAM_REQ_TERMS required
+    terms). Raised, never dropped: a dropped requirement places the pod wrongly."""
 
 
 @dataclass(frozen=True)
@@ -251,6 +253,27 @@ class NodeSelectorRequirement:
 class PreferredTerm:
     weight: int  # 1..100 (API validation)
     requirements: List[NodeSelectorRequirement] = field(default_factory=list)
+
+
+@dataclass(frozen=True)
+class MatchField:
+    """A matchFields requirement of a nodeSelectorTerm (metadata.name). The
+    records carry no node names, so a term holding one is refused."""
+    key: str = "metadata.name"
+    operator: str = "In"
+    values: Tuple[str, ...] = ()
+
+
+@dataclass
+class RequiredAffinity:
+    """What NodeAffinity's Filter reads of a pod (k8s@v1.22.0 component-helpers
+    nodeaffinity GetRequiredNodeAffinity): spec.nodeSelector, every pair ANDed,
+    and requiredDuringSchedulingIgnoredDuringExecution's nodeSelectorTerms, ORed
+    (each a list of matchExpressions, ANDed). terms None: no required affinity;
+    []: a required selector without terms, which matches nothing, as does a term
+    without expressions."""
+    node_selector: Dict[str, str] = field(default_factory=dict)
+    terms: Optional[List[List[NodeSelectorRequirement]]] = None
 
 
 def parse_int64(v: str) -> Optional[int]:
@@ -306,10 +329,11 @@ class NamTerms:
                 m |= 1 << vid
         return m
 
-    def term(self, t: PreferredTerm) -> Tuple[int, int, int]:
-        if not 1 <= t.weight <= 100:
-            raise ValueError("PreferredSchedulingTerm weight must be in 1..100 (API validation)")
-        for r in t.requirements:
+    def check(self, reqs) -> None:
+        """Refuses what the records cannot express; API validation of the rest."""
+        for r in reqs:
+            if isinstance(r, MatchField):
+                raise UnsupportedTerm("matchFields (metadata.name): the records carry no node names")
             if r.key not in self.keys:
                 raise UnsupportedTerm(f"requirement on label {r.key!r}: the records carry {self.keys} only")
             if r.operator not in NAM_OPERATORS:
@@ -320,6 +344,11 @@ class NamTerms:
                 raise ValueError(f"{r.operator} takes no values (API validation)")
             if r.operator in ("Gt", "Lt") and (len(r.values) != 1 or parse_int64(r.values[0]) is None):
                 raise ValueError(f"{r.operator} needs one integer value (API validation)")
+
+    def term(self, t: PreferredTerm) -> Tuple[int, int, int]:
+        if not 1 <= t.weight <= 100:
+            raise ValueError("PreferredSchedulingTerm weight must be in 1..100 (API validation)")
+        self.check(t.requirements)
         if not t.requirements:
             return (t.weight, 0, 0)
         return (t.weight,) + tuple(self.id_set(k, [r for r in t.requirements if r.key == self.keys[k]])
@@ -333,6 +362,41 @@ class NamTerms:
             if len(terms) > NAM_TERMS:
                 raise UnsupportedTerm(f"more than {NAM_TERMS} preferred terms")
         return nam_term_sets_ext_array([[self.term(t) for t in terms] for terms in sets])
+
+    def required(self, a: "RequiredAffinity") -> Optional[List[Tuple[int, int]]]:
+        """One pod's requirement as nam_required_sets_array takes it: None, or per
+        required term its two id sets with the nodeSelector folded in (a pair
+        k: v is the requirement k In [v]; a pod with only a nodeSelector has one
+        term). An empty term and a selector without terms match nothing: (0, 0)."""
+        from ._lib import NAM_REQ_TERMS
+
+        sel = [NodeSelectorRequirement(k, "In", (v,)) for k, v in a.node_selector.items()]
+        self.check(sel)
+        for t in a.terms or []:
+            self.check(t)
+        if a.terms is None:
+            if not sel:
+                return None
+            terms = [[]]
+        else:
+            if len(a.terms) > NAM_REQ_TERMS:
+                raise UnsupportedTerm(f"more than {NAM_REQ_TERMS} required nodeSelectorTerms")
+            terms = a.terms
+        out = []
+        for t in terms:
+            if a.terms is not None and not t:
+                out.append((0, 0))  # an empty nodeSelectorTerm matches nothing, whatever the selector
+                continue
+            out.append(tuple(self.id_set(k, [r for r in sel + list(t) if r.key == self.keys[k]]) for k in (0, 1)))
+        return out or [(0, 0)]
+
+    def required_sets(self, sets: List["RequiredAffinity"]) -> np.ndarray:
+        """uint8 (n, 260) ms_nam_required_set records; set i is set id i + 1 (the id
+        that also names the pod's preferred term set). As with term_sets, the shim
+        re-registers them when a value-id table grows."""
+        from ._lib import nam_required_sets_array
+
+        return nam_required_sets_array([self.required(a) for a in sets])
 
 
 def pod_requests(p: Pod, check_resources: bool = True):

@@ -202,6 +202,55 @@ def nam_term_sets_ext(k: int, seed: int = 1, n_zone: int = N_ZONES, n_label2: in
     return nam_term_sets_ext_array(sets)
 
 
+def nam_required_sets(k: int, seed: int = 1, n_zone: int = N_ZONES, n_label2: int = N_LABEL2) -> np.ndarray:
+    """K random required sets (uint8 (K, 260), ms_nam_required_set) for the ids of
+    nam_term_sets(_ext): about a third carry no requirement, the rest 1..4 terms
+    in the operator mix of nam_term_sets_ext (In, NotIn, Exists, DoesNotExist, Gt,
+    Lt on one or both keys, sometimes two requirements on one key), about 1 term
+    in 16 empty (matches nothing)."""
+    from ._lib import nam_required_sets_array
+
+    rng = np.random.default_rng(int(seed) * 104729 + k)
+    top = {0: n_zone, 1: n_label2}
+    full = (1 << 256) - 1
+
+    def ids(kk):
+        pool = list(range(1, top[kk] + 1)) + [255]
+        return [int(x) for x in rng.choice(pool, size=int(rng.integers(1, 4)), replace=False)]
+
+    def req_mask(kk):
+        op = int(rng.integers(0, 6))
+        if op == 0:  # In
+            return sum(1 << v for v in set(ids(kk)))
+        if op == 1:  # NotIn
+            return full & ~sum(1 << v for v in set(ids(kk)))
+        if op == 2:  # Exists
+            return full & ~1
+        if op == 3:  # DoesNotExist
+            return 1
+        t = int(rng.integers(0, top[kk] + 1))
+        return sum(1 << v for v in range(t + 1, 256)) if op == 4 else sum(1 << v for v in range(1, t))
+
+    sets = []
+    for _ in range(k):
+        if rng.integers(0, 3) == 0:
+            sets.append(None)
+            continue
+        terms = []
+        for _ in range(int(rng.integers(1, 5))):
+            if rng.integers(0, 16) == 0:
+                terms.append((0, 0))
+                continue
+            which = int(rng.integers(0, 3))  # 0: zone only, 1: label2 only, 2: both
+            zm = req_mask(0) if which in (0, 2) else full
+            lm = req_mask(1) if which in (1, 2) else full
+            if which == 2 and rng.integers(0, 3) == 0:
+                zm &= req_mask(0)  # two requirements on one key: ANDed
+            terms.append((zm, lm))
+        sets.append(terms)
+    return nam_required_sets_array(sets)
+
+
 def set_tolerations(rec: np.ndarray, tol_hard, tol_soft) -> None:
     """MS_PLUGINS_NU_TT_NN: bit t of tol_hard / tol_soft = some toleration of the
     pod tolerates NoSchedule / PreferNoSchedule taint id t (ms_pod_rec.tol_hard,
