@@ -197,8 +197,8 @@ def test_nam_ext_against_literal_loop(oracle, n_nodes, n_pods, n_sets, seed):
 
 
 def test_nam_ext_many_classes_and_unknown_sets(oracle):
-    # more (term set, toleration) classes than the class sort holds (pods then in batch
-    # order), term set ids past the registered ones (no terms), a chunked host call
+    # many sorted classes (at most 2 x 1,201 x 11 digits = 26,422 buckets, within the class
+    # sort's 65,536), term set ids past the registered ones (no terms), a chunked host call
     seed = 66
     nr, pr, ts = _ext_cluster(1500, 5000, 1200, seed)
     sid = (np.arange(len(pr)) * 7919) % 1400  # ids 1201..1399: not registered
@@ -208,6 +208,25 @@ def test_nam_ext_many_classes_and_unknown_sets(oracle):
         _same(_device_cycle(e, pr), o, "many classes")
     with _engine(nr, ts, seed, max_batch=1700) as e:
         _same(e.schedule(pr, _lib.MODE_BATCHED), o, "many classes, host chunks")
+
+
+def test_nam_ext_more_classes_than_the_class_sort_holds(oracle):
+    # 3,200 sets: all 6,400 (set, toleration) classes in ONE chunk, 6,402 x 11 = 70,422 buckets
+    # past the class sort's 65,536, so the pods keep batch order (ctl[1] == 0, rep[c] by
+    # atomicMin, perm[i] = i); 1,600 more pods repeat 40 classes at distant batch positions
+    seed = 71
+    nr, pr, ts = _ext_cluster(300, 8000, 3200, seed)
+    rng = np.random.default_rng(seed)
+    cls = np.concatenate([rng.permutation(6400), np.tile(rng.choice(6400, 40, replace=False), 40)])
+    cls[6400:] = rng.permutation(cls[6400:])
+    cls[[0, 7999]] = cls[[7999, 0]]  # (a repeated class first in the batch, a single one last)
+    sid = 1 + cls // 2
+    pr["pref_zone"], pr["pref_weight"], pr["tolerates_unschedulable"] = sid & 0xFF, sid >> 8, cls & 1
+    assert len(set(cls.tolist())) == 6400 and 6402 * 11 > 65536
+    o = _oracle(oracle, nr, pr, ts, seed)
+    with _engine(nr, ts, seed) as e:
+        _same(_device_cycle(e, pr), o, "unsorted classes, device")
+        _same(e.schedule(pr, _lib.MODE_BATCHED), o, "unsorted classes, host")
 
 
 @pytest.mark.parametrize("weights", [(1, 1), (3, 2)])
