@@ -110,7 +110,7 @@ struct CommState {
     uint64_t drains = 0, cs_drain_seen = 0;        // drains enqueued / the newest the collective stream waited for
     bool two_streams = false;  // MINISCHED_SHARD_STREAMS=2: sweeps alternate over ss[0], ss[1] (A/B)
     bool reads_outstanding = false;                // sweeps since the last fence
-    uint64_t ctx_seen = ~0ull;                     // ctx_seq the sweep streams were last ordered after
+    uint64_t ctx_seen = ~0ull;                     // order.seq() the sweep streams were last ordered after
     hipStream_t ctx_seen_stream = nullptr;         // (and the caller's stream then)
     ShardSlot slot[kPipeMax];
     std::deque<Pending> pending;
@@ -281,11 +281,11 @@ int prepare_locked(ms_ctx *c, uint32_t n, hipStream_t s, uint32_t &si, hipStream
         MS_HIP(c, hipEventRecord(m.ev_in, s));
         MS_HIP(c, hipStreamWaitEvent(X, m.ev_in, 0));
     }
-    if (m.ctx_seen != c->ctx_seq || m.ctx_seen_stream != s) {
+    if (m.ctx_seen != c->order.seq() || m.ctx_seen_stream != s) {
         MS_HIP(c, hipEventRecord(m.ev_ctx, c->stream));
         MS_HIP(c, hipStreamWaitEvent(X, m.ev_ctx, 0));
         if (m.two_streams) MS_HIP(c, hipStreamWaitEvent(m.ss[xi ^ 1], m.ev_ctx, 0));
-        m.ctx_seen = c->ctx_seq;
+        m.ctx_seen = c->order.seq();
         m.ctx_seen_stream = s;
     }
     // the slot's previous collective (submission k - depth - 1) read the keys
@@ -562,7 +562,7 @@ void comm_free(ms_ctx *c) {
 int comm_cycle_staged(ms_ctx *c, uint32_t n, int32_t mode) {
     CommState &m = *c->comm;
     const hipStream_t s = c->stream;
-    ++c->ctx_seq;  // binds below write the table on the context stream
+    c->order.wrote_ctx();  // binds below write the table on the context stream
     if (mode == MS_MODE_SEQUENTIAL && !plugins_stateless(c)) return seq_sharded_locked(c, n, c->d_pods, c->d_res, s);
     (void)m;
     return batched_all_locked(c, n, c->d_pods, c->d_res, s, true);

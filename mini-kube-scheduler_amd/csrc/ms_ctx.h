@@ -1,6 +1,8 @@
-// ms_ctx.h — the engine context behind the C ABI, shared by ms_capi.cpp (one
-// device's node shard, deltas, staging, streams) and ms_comm.cpp (the RCCL
-// communicator and node-sharded pipelines). Not part of the public boundary.
+// ms_ctx.h — the engine context behind the C ABI, shared by the host layer
+// (ms_capi.cpp: one device's node shard, deltas, staging, streams; ms_cycle.cpp,
+// ms_seq_host.cpp, ms_hostarray.cpp, ms_nam_tab.cpp: the cycles above it) and
+// ms_comm.cpp (the RCCL communicator and node-sharded pipelines). Not part of
+// the public boundary.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +17,7 @@
 
 #include "ms_copy_pool.h"
 #include "ms_internal.h"
+#include "ms_order.h"
 #include "ms_owned.h"
 
 namespace msgpu {
@@ -72,6 +75,14 @@ using Stream = Owned<StreamRes>;
 
 // For MS_HIP around an owner's alloc / ensure: the runtime's error behind a false.
 inline hipError_t made(bool ok) { return ok ? hipSuccess : hipGetLastError(); }
+
+// The runtime calls of ms_order.h; the events are created on first use.
+struct HipOrder {
+    using stream = hipStream_t;
+    using event = Event;
+    static bool record(Event &e, hipStream_t s) { return e.ensure() && hipEventRecord(e, s) == hipSuccess; }
+    static bool wait(hipStream_t s, Event &e) { return hipStreamWaitEvent(s, e, 0) == hipSuccess; }
+};
 }  // namespace msgpu
 
 using msgpu::DevBuf;
@@ -174,23 +185,9 @@ struct ms_ctx {
     DevBuf<ms_seq_cand> d_merged;
     DevBuf<uint32_t> d_merged_flags;
 
-    // Ordering. Every piece of work that reads or writes the node table or the
-    // context's scratch is totally ordered through the context stream: a call
-    // on a caller stream first waits for the context stream (order_after_ctx_
-    // stream), and its work is then chained back into the context stream
-    // (chain_back), so later deltas, binds, read-backs and calls on any other
-    // stream wait for it. ctx_seq counts enqueues on the context stream that a
-    // caller stream has not necessarily seen; a caller stream ordered after it
-    // at ctx_seq needs no new cross-stream wait (each costs ~6-10 us of idle
-    // device time even when already signalled, tools/ubench/xstream).
-    uint64_t ctx_seq = 0;
-    // fence_seq counts the times the context stream was made to wait for the
-    // communicator's in-flight sweeps (table readers on its internal streams,
-    // comm_fence_reads); a stream ordered before the last fence must wait again
-    uint64_t fence_seq = 0, ordered_fence = 0;
-    hipStream_t ordered_stream = nullptr;  // (not owned: a caller's)
-    uint64_t ordered_seq = 0;
-    Event ev_order, ev_back;
+    // every access to the table or the scratch above, on whichever stream, is
+    // ordered through the context stream (ms_order.h; OrderedCall below)
+    msgpu::StreamOrder<msgpu::HipOrder> order;
 
     // RCCL communicator and the node-sharded pipelines (ms_comm.cpp); null
     // until ms_comm_init
@@ -243,21 +240,67 @@ class CallClock {
 
 constexpr uint32_t kTopKCands = 4;  // ms_seq_cand entries per pod and shard (the validator's top-K)
 
+// validator counters (d_overflow): u32[6] (overflow, re-swept tiles, recomputes, pods, speculation
+// misses, list scans), then u64[4] phase cycles in the MS_VSTAMPS diagnostic build
+constexpr size_t kStatsBytes = 256;
+
 // ms_capi.cpp (callers hold sched_mu)
 int flush_locked(ms_ctx *c);
 hipStream_t pick_stream(ms_ctx *c, void *s);
-int order_after_ctx_stream(ms_ctx *c, hipStream_t s);
-int chain_back(ms_ctx *c, hipStream_t s, bool recorded = false);
-int ensure_tiles(ms_ctx *c, uint32_t n_tiles);
 int ensure_stage(ms_ctx *c, uint32_t n);
-// MS_PLUGINS_NU_TT_NN: this shard's merged per-pod summaries (MS_TT_SUMMARY_BYTES each) into out
-int tt_summaries_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, void *out, hipStream_t s);
 bool plugins_stateless(const ms_ctx *c);
+
+// One ordered device call (ms_order.h): the whole prologue of an entry point
+// whose work touches the node table or the context's scratch, and its
+// epilogue. The constructor locks sched_mu, sets the device, drains the node
+// deltas (flush; not for the calls that must leave them queued), picks the
+// stream and orders it after the context stream; done() chains the call's
+// work back. A call that fails returns its code without done().
+//     OrderedCall call(c, stream);
+//     if (call.rc()) return call.rc();
+//     ... launches on call.stream() ...
+//     return call.done();
+class OrderedCall {
+  public:
+    OrderedCall(ms_ctx *c, void *stream, bool flush = true);
+    int rc() const { return rc_; }
+    hipStream_t stream() const { return s_; }
+    // On a caller stream: the chain-back event, for a dispatch that records it
+    // itself after the call's last launch (then done(true)); null on the context stream.
+    hipEvent_t back_event() const { return back_; }
+    int done(bool recorded = false);
+
+  private:
+    ms_ctx *c_;
+    std::lock_guard<std::mutex> g_;
+    hipStream_t s_ = nullptr;
+    hipEvent_t back_ = nullptr;
+    int rc_ = MS_OK;
+};
+
+// ms_cycle.cpp: the per-plugin-set cycle drivers
 // done (optional): recorded on s after the sweep (by the K1 dispatch itself when it is one launch)
 int sweep_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, unsigned long long *keys, uint32_t *flags,
                  hipStream_t s, hipEvent_t done = nullptr);
+// done (optional): recorded on s after the call's last launch
+int select_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_result *d_res, hipStream_t s,
+                  int commit = 0, hipEvent_t done = nullptr);
+// MS_PLUGINS_NU_TT_NN: the batch's summaries merged into out (this shard's, MS_TT_SUMMARY_BYTES
+// per pod), or with out null the single-shard cycle into results
+int tt_cycle_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, void *out, ms_result *results, int commit,
+                    hipStream_t s);
+// MS_PLUGINS_NU_TT_NN scratch of at least `need` bytes (the two-pass bit-sliced
+// cycle's, or the node shards' summaries).
+int ensure_tt(ms_ctx *c, size_t need);
+
+// ms_seq_host.cpp: the sequential engine's host side
+int ensure_tiles(ms_ctx *c, uint32_t n_tiles);
+int run_sequential(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, ms_result *d_res, hipStream_t s);
 int seq_candidates_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, ms_seq_cand *cands_dev,
                           uint32_t *flags_dev, hipStream_t s);
+// The diagnostic builds' read-out at ms_destroy (MS_VSTAMPS counters to stderr,
+// the MS_TIMELINE file); nothing in the product build.
+void seq_diag_readout(ms_ctx *c);
 
 // ms_comm.cpp
 void comm_free(ms_ctx *c);
@@ -275,8 +318,5 @@ void comm_rank_world(const ms_ctx *c, int32_t *rank, int32_t *world);
 // communicator's internal streams; returns 1 if it inserted waits, 0 if none
 // were outstanding (or no communicator), < 0 on failure.
 int comm_fence_reads(ms_ctx *c, hipStream_t writer);
-// MS_PLUGINS_NU_TT_NN scratch of at least `need` bytes (the two-pass bit-sliced
-// cycle's, or the node shards' summaries).
-int ensure_tt(ms_ctx *c, size_t need);
 
 }  // namespace msgpu

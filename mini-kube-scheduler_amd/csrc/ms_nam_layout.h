@@ -1,7 +1,7 @@
 // MS_PLUGINS_NU_NN_NAM scratch arithmetic: how a call is cut into chunks, the
 // row segments of the per-class passes, where each scratch array starts, how
 // much the context allocates, and where the node-shard inputs (after / m_in)
-// sit. Host only, plain integers, no HIP: ms_affinity.hip and ms_capi.cpp use
+// sit. Host only, plain integers, no HIP: ms_affinity.hip and ms_cycle.cpp use
 // this one copy, and tests/cpp/test_nam_layout.cpp sweeps it on the CPU.
 //
 // The rule the rest depends on: ONE NamPlan per call. The allocation is sized

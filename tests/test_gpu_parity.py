@@ -647,6 +647,40 @@ def test_stream_ordering_deltas_binds_reads(oracle):
     assert np.array_equal(t["pod_count"][keep], placed[keep])
 
 
+@pytest.mark.parametrize("plugin_set", [_lib.PLUGINS_NU_NN_NA, PLUGINS_NU_NRF_NN_LA])
+def test_stream_ordering_mixed_null_and_caller_stream(oracle, plugin_set):
+    # Calls on the context stream (stream=None) and on one caller stream alternate on one
+    # context with no host sync between them; both plugin sets sweep every call into the
+    # context's one key / flag scratch, so each call must follow the one before it on the
+    # other stream (csrc/ms_order.h; the caller / context / caller sequence of
+    # tests/cpp/test_order.cpp, which is the proof: this cannot force the overlap). A
+    # different pod batch per round; no binds, so every round sees the same table.
+    import torch
+
+    dev = torch.device("cuda:0")
+    s = torch.cuda.Stream(device=dev)
+    n, p, rounds, seed = 5000, 700, 6, 77
+    na = plugin_set == _lib.PLUGINS_NU_NN_NA
+    nr = synth.nodes(n, seed=seed, zones=na, resources=not na)
+    batches = [synth.pods(p, seed=seed + 1 + k, zones=na, resources=not na) for k in range(rounds)]
+    for pr in batches:
+        pr["tolerates_unschedulable"][::6] = 1
+    pods_d = [torch.from_numpy(pr.view(np.uint8).copy()).to(dev) for pr in batches]
+    outs = [torch.empty(p * 24, dtype=torch.uint8, device=dev) for _ in range(rounds)]
+    with engine_with(nr, plugin_set=plugin_set, seed=seed) as e:
+        torch.cuda.synchronize()
+        for k in range(rounds):
+            e.select_batch_device(p, pods_d[k].data_ptr(), outs[k].data_ptr(), s.cuda_stream if k & 1 else None)
+        e.read(0, 1)  # context stream: after every round on either stream
+        s.synchronize()
+    for k, pr in enumerate(batches):
+        if na:
+            o = oracle.schedule_na(nr, pr, literal=False, seed=seed)
+        else:
+            o = oracle.schedule(nr, pr, plugin_set=1, mode=0, seed=seed)
+        assert_same(outs[k].cpu().numpy().view(_lib.RESULT), o)
+
+
 @pytest.mark.parametrize("weights", [(1, 1), (2, 3), (10, 10)])
 @pytest.mark.parametrize("n_nodes,n_pods", [(1, 5), (17, 64), (300, 200), (5000, 700), (40_000, 300)])
 def test_na_batched(oracle, weights, n_nodes, n_pods):
@@ -718,7 +752,7 @@ def test_host_arrays_zero_copy_chunks(oracle, n_pods):
     with engine_with(nr, seed=seed) as e:
         assert_same(e.schedule(pr, MODE_BATCHED), o)
         prof = e.last_call_profile()
-        assert prof["chunks"] == max(1, min(4, n_pods // 50_000)) and prof["total"] > 0  # (ms_capi.cpp kZcMinChunk)
+        assert prof["chunks"] == max(1, min(4, n_pods // 50_000)) and prof["total"] > 0  # (ms_hostarray.cpp kZcMinChunk)
         assert_same(e.schedule(pr, MODE_SEQUENTIAL), o)
         r = e.schedule_compact(_lib.compact_pods(pr))
         for k_res, k_or in (("node", "node"), ("code", "code"), ("score", "score"), ("plugin_mask", "mask")):

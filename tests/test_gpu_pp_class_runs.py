@@ -28,7 +28,7 @@ def _cus():
 
 def _n_pods(waves=16, per_chunk=100):
     # chunks of at least per_chunk pods (module docstring); one host chunk per
-    # call (ms_capi.cpp splits calls of 100,000 pods and more)
+    # call (ms_hostarray.cpp splits calls of 100,000 pods and more)
     slots = _cus() * (16 // waves)
     n = min(per_chunk * slots, 99_999)
     assert n // slots // 8 * 8 >= 80, "chunks too small for the class sort"

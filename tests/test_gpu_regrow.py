@@ -1,7 +1,7 @@
 """Scratch that grows inside a live context, and contexts that give their memory back.
 
 Every grow-on-demand routine of the host layer (mini-kube-scheduler_amd/csrc/ms_capi.cpp,
-ms_comm.cpp; DESIGN.md "Who frees what") releases the buffers it held and allocates larger
+ms_cycle.cpp, ms_seq_host.cpp, ms_hostarray.cpp, ms_comm.cpp; DESIGN.md "Who frees what") releases the buffers it held and allocates larger
 ones. Each case here takes ONE context, makes a call, then a larger call that forces the
 routine to grow, and compares both results bit for bit with the CPU oracle: a buffer
 released while still in use, a stale capacity or a view left pointing into a released

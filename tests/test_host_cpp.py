@@ -151,8 +151,27 @@ def test_owned_asan(tmp_path):
     assert out.splitlines()[-1] == "0 failed", out
 
 
+def test_stream_order_model_asan(tmp_path):
+    # the cross-stream ordering protocol (csrc/ms_order.h, the copy ms_ctx.h instantiates with the HIP
+    # calls) over a model of streams and events that tracks happens-before sets: every piece of work
+    # follows every earlier ordered one in all call sequences up to length 6 and in seeded random ones
+    # of length 50, with as many records and waits as the rule it replaced wherever that rule held; the
+    # caller / context / caller sequence that rule missed is a named case the model must see fail
+    exe = str(tmp_path / "test_order")
+    src = os.path.join(ROOT, "tests", "cpp", "test_order.cpp")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+                    "-I", os.path.join(PKG, "csrc"), src, "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = _run([exe], env=env)
+    print(out)
+    lines = out.splitlines()
+    assert lines[-1] == "0 failed", out
+    assert int(lines[0].split()[6]) == 67_368_420, out  # "sequences up to length 6 checked: N"
+    assert int(lines[1].split()[6]) == 4000, out  # "random sequences of length 50 checked: N"
+
+
 def test_nam_layout_plan_asan(tmp_path):
-    # the NodeAffinity scratch plan (csrc/ms_nam_layout.h, the copy ms_affinity.hip and ms_capi.cpp
+    # the NodeAffinity scratch plan (csrc/ms_nam_layout.h, the copy ms_affinity.hip and ms_cycle.cpp
     # use): every chunk of a call, the short last one included, fits the call's allocation; and the
     # shapes of tests/test_gpu_chunks.py sit where the rule before it (a layout per chunk) overran
     exe = str(tmp_path / "test_nam_layout")
