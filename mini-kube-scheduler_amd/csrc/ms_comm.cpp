@@ -20,14 +20,14 @@
 //          NodeAffinity set: uint32 MAX of the normalise anchors;
 // -> the decode of the slice on the caller's stream. Pipelined: the decodes of
 // batch k are enqueued once `depth` later batches were submitted, so batch k's
-// collective overlaps their sweeps (RCCL runs one communicator's collectives in
-// issue order on the collective stream, so a drain waits for the newest only).
-// The sweeps run on the caller's stream, the collectives on the collective
-// stream and the decodes on a decode stream, so no sweep waits for a
-// collective or a decode (one cross-queue wait per step: the collective on
-// its sweep). The sweeps only read the node table; writers (deltas, binds) are
-// fenced behind the in-flight ones (comm_fence_reads) instead of every sweep
-// being chained into the context stream. MINISCHED_SHARD_STREAMS=2 alternates
+// collective overlaps their sweeps. The sweeps run on the caller's stream, the
+// collectives on the collective stream and the decodes on a decode stream, so
+// no sweep waits for a collective or a decode (one cross-queue wait per step:
+// the collective on its sweep). The sweeps only read the node table; writers
+// (deltas, binds) are fenced behind the in-flight ones (comm_fence_reads)
+// instead of every sweep being chained into the context stream. When each of
+// these may run is ms_shard_order.h's (ShardOrder, with the argument for every
+// wait); this file says what to launch. MINISCHED_SHARD_STREAMS=2 alternates
 // the sweeps over two internal streams instead (two independent streams on
 // separate hardware queues overlap one sweep's ramp and tail with the next:
 // 55.4 vs 42.9 us per 12.5k-row sweep, tools/probe_streams.py; but the
@@ -53,6 +53,7 @@
 #include <new>
 
 #include "ms_ctx.h"
+#include "ms_shard_order.h"
 
 // The RCCL entry points. `make comm-loopback` (tests only) builds this file with
 // -DMS_COMM_LOOPBACK against an in-process rendezvous of G contexts on one GPU
@@ -83,15 +84,19 @@ struct ShardSlot {
     // stride = the batch), and the slice's plans for the final pass
     DevBuf<void> cen_mine, cen_all, plans;
     uint32_t cap = 0;       // pods per slice the buffers hold
-    bool used = false;      // a batch went through this slot
-    uint64_t dec_gen = 0;   // the drain that decoded its last batch
 };
 
-struct Pending {
-    uint32_t slot, n, first, count;
-    const ms_pod_rec *pods;  // the batch (decode reads pods + first)
-    ms_result *results;      // this rank's slice
+// A batch from its submission to its decode (its slot's buffers may be swept
+// again by a later one before the decode is enqueued: the payload is not the slot's).
+struct Batch {
+    uint32_t slot = 0, n = 0, first = 0, count = 0;
+    const ms_pod_rec *pods = nullptr;  // the batch (decode reads pods + first)
+    ms_result *results = nullptr;      // this rank's slice
+    hipStream_t X = nullptr;           // its sweep stream
 };
+
+using Order = ShardOrder<HipOrder>;
+static_assert(kPipeMax == Order::kSlotsMax, "one buffer set per ordering slot");
 
 }  // namespace
 
@@ -103,22 +108,14 @@ struct CommState {
     Stream cs;     // collective stream
     Stream ss[2];  // sweep streams, alternating batch by batch
     Stream ds;     // decode stream (the drains; callers wait on it in ms_sharded_drain)
-    Event ev_swept[kPipeMax], ev_comb[kPipeMax];
-    Event ev_ag[kPipeMax];  // TaintToleration two-pass: the slot's census all-gather
-    Event ev_in, ev_ctx;    // caller stream -> sweep stream, context stream -> sweep stream
-    Event ev_drained;       // after the newest drain's decodes (decode stream)
-    uint64_t drains = 0, cs_drain_seen = 0;        // drains enqueued / the newest the collective stream waited for
-    bool two_streams = false;  // MINISCHED_SHARD_STREAMS=2: sweeps alternate over ss[0], ss[1] (A/B)
-    bool reads_outstanding = false;                // sweeps since the last fence
-    uint64_t ctx_seen = ~0ull;                     // order.seq() the sweep streams were last ordered after
-    hipStream_t ctx_seen_stream = nullptr;         // (and the caller's stream then)
+    // when each step of a batch may run: every event and counter of the
+    // pipeline, the slots' state and the pending ring (ms_shard_order.h).
+    // depth: batches in flight before the oldest are decoded; two_streams
+    // (MINISCHED_SHARD_STREAMS=2): sweeps alternate over ss[0], ss[1] (A/B)
+    Order order;
     ShardSlot slot[kPipeMax];
-    std::deque<Pending> pending;
-    uint64_t submitted = 0;
-    uint64_t x_comb_seen = 0;       // x_stream waited for the collectives of submissions < this
-    hipStream_t x_stream = nullptr;
-    uint32_t depth = 4, group = 4;
-    Event ev_ds;
+    std::deque<Batch> pending;  // after their collectives, oldest first (in step with order's ring)
+    CommState(uint32_t depth, bool two_streams) : order(depth, two_streams) {}
     // node-sharded exact sequential
     uint32_t seq_w = 0;
     DevBuf<ms_pod_rec> win_pods;
@@ -128,14 +125,9 @@ struct CommState {
     DevBuf<ms_seq_cand> cands, cands_all, merged;
     DevBuf<uint32_t> sflags, sflags_all, merged_flags;
     uint64_t seq_windows = 0, seq_rounds = 0;
-    // coalesced submits: a NU+NN submission whose sweep waits to share the next one's launch
-    struct Stash {
-        bool on = false;
-        uint32_t n = 0, si = 0;
-        const ms_pod_rec *pods = nullptr;
-        ms_result *results = nullptr;
-        hipStream_t X = nullptr;
-    } stash;
+    // coalesced submits: a NU+NN submission whose sweep waits to share the
+    // next one's launch (while order.held())
+    Batch stash;
     bool coalesce = true;
     // MINISCHED_HOST_PROF=1: host time of ms_sharded_submit's phases (ns), printed at ms_destroy
     bool host_prof = false;
@@ -166,17 +158,34 @@ namespace {
             return fail((c), MS_E_RCCL, std::string(#call) + ": " + CCL(ncclGetErrorString)(r_));      \
     } while (0)
 
-// Buffers of a slot for slices of `per` pods, rounded up to 1024 (grown; the
+// A step of the ordering class (false: a record or a wait failed, or a step
+// was taken while a submission was still held back).
+#define MS_ORD(c, call)                                                                            \
+    do {                                                                                           \
+        if (!(call))                                                                               \
+            return fail((c), MS_E_HIP, std::string("stream ordering (" #call "): ") +              \
+                                           hipGetErrorString(hipGetLastError()));                  \
+    } while (0)
+
+int drain_locked(ms_ctx *c, size_t k);
+
+// Buffers of slot si for slices of `per` pods, rounded up to 1024 (grown; the
 // slot's previous batch has been drained). No synchronise of its own: the
 // runtime's free of the old blocks waits for that batch's decode, so the slot
 // starts over as unused.
-int slot_ensure(ms_ctx *c, ShardSlot &sl, uint32_t per) {
+int slot_ensure(ms_ctx *c, uint32_t si, uint32_t per) {
+    ShardSlot &sl = c->comm->slot[si];
     if (per <= sl.cap) return MS_OK;
     const size_t G = (size_t)c->comm->world;
     const uint32_t cap = std::max<uint32_t>(1024u, cdiv(per, 1024u) * 1024u);
+    // (a submission held back for a partner makes the slot come round one
+    // step early, its batch not decoded yet: that decode reads these buffers)
+    if (const size_t k = c->comm->order.pending_through(si)) {
+        const int rc = drain_locked(c, k);
+        if (rc) return rc;
+    }
     sl.cap = 0;
-    sl.used = false;
-    sl.dec_gen = 0;
+    MS_ORD(c, c->comm->order.regrown(si));
     if (!sl.keys.alloc(G * cap) || !sl.keys_mine.alloc(cap) || !sl.flags.alloc(G * cap) || !sl.flags_mine.alloc(cap) ||
         (c->cfg.plugin_set == MS_PLUGINS_NU_TT_NN &&
          (!sl.cen_mine.alloc(G * cap * MS_TT_CENSUS_BYTES) || !sl.cen_all.alloc(G * G * cap * MS_TT_CENSUS_BYTES) ||
@@ -198,12 +207,11 @@ void slice_of(const CommState &m, uint32_t n, uint32_t &first, uint32_t &count) 
 int drain_locked(ms_ctx *c, size_t k) {
     CommState &m = *c->comm;
     const hipStream_t s = m.ds;
-    k = std::min(k, m.pending.size());
+    MS_ORD(c, m.order.drain_begin(k));
     if (k == 0) return MS_OK;
-    MS_HIP(c, hipStreamWaitEvent(s, m.ev_comb[m.pending[k - 1].slot], 0));  // collectives run in issue order
     if (c->cfg.plugin_set == MS_PLUGINS_NU_TT_NN) {  // the slice's plans + the MAX of the picks
         for (size_t i = 0; i < k; ++i) {
-            const Pending &p = m.pending[i];
+            const Batch &p = m.pending[i];
             const ShardSlot &sl = m.slot[p.slot];
             MS_HIP(c, launch_tt2_final_shard(c->t, c->rows_dev, p.pods + p.first, p.count, seed32_of(c->cfg.seed),
                                              sl.plans, p.count, static_cast<const char *>(sl.cen_all.get()) +
@@ -212,7 +220,7 @@ int drain_locked(ms_ctx *c, size_t k) {
         }
     } else if (c->cfg.plugin_set == MS_PLUGINS_NU_NN_NA) {
         for (size_t i = 0; i < k; ++i) {
-            const Pending &p = m.pending[i];
+            const Batch &p = m.pending[i];
             const ShardSlot &sl = m.slot[p.slot];
             MS_HIP(c, launch_decode_na(p.pods + p.first, p.count, sl.keys_mine, sl.flags_mine, 0, seed32_of(c->cfg.seed),
                                        c->w_nn, c->w_na, p.results, s));
@@ -221,31 +229,28 @@ int drain_locked(ms_ctx *c, size_t k) {
         SliceJob jobs[kMaxSliceJobs];
         const bool nrf = c->cfg.plugin_set == MS_PLUGINS_NU_NRF_NN_LA;
         for (size_t i = 0; i < k; ++i) {
-            const Pending &p = m.pending[i];
+            const Batch &p = m.pending[i];
             const ShardSlot &sl = m.slot[p.slot];
             jobs[i] = SliceJob{p.pods + p.first, sl.keys_mine, nrf ? sl.flags_mine : nullptr, nullptr, p.results,
                                p.count, 0};
         }
         MS_HIP(c, launch_decode_slices(jobs, (uint32_t)k, s));
     }
-    ++m.drains;
-    for (size_t i = 0; i < k; ++i) m.slot[m.pending[i].slot].dec_gen = m.drains;
-    MS_HIP(c, hipEventRecord(m.ev_drained, s));
+    MS_ORD(c, m.order.drain_end(k));
     m.pending.erase(m.pending.begin(), m.pending.begin() + (long)k);
     return MS_OK;
 }
 
-// Everything pending decoded; then `s` waits for the decode stream.
 int flush_stash(ms_ctx *c);
 
+// Everything pending decoded; then `s` waits for the decode stream.
 int drain_to(ms_ctx *c, hipStream_t s) {
     CommState &m = *c->comm;
     int rc = flush_stash(c);  // (a coalesced submission waiting for a partner)
     if (rc) return rc;
-    rc = drain_locked(c, m.pending.size());
+    rc = drain_locked(c, m.order.pending());
     if (rc) return rc;
-    MS_HIP(c, hipEventRecord(m.ev_ds, m.ds));
-    MS_HIP(c, hipStreamWaitEvent(s, m.ev_ds, 0));
+    MS_ORD(c, m.order.drained_to(s));
     return MS_OK;
 }
 
@@ -261,72 +266,18 @@ inline void host_tick(CommState &m, int i, HostClock::time_point &t) {
 // sweeps of a shard one workgroup holds, on one sweep stream.
 bool coalescable(const ms_ctx *c) {
     const CommState &m = *c->comm;
-    return m.coalesce && !m.two_streams && c->cfg.plugin_set == MS_PLUGINS_NU_NN && c->rows_dev <= kPpMaxFusedRows;
+    return m.coalesce && !m.order.two_streams() && c->cfg.plugin_set == MS_PLUGINS_NU_NN &&
+           c->rows_dev <= kPpMaxFusedRows;
 }
 
-// The sweep stream and slot of the next submission (the slot's buffers sized
-// for n pods), ordered after: the caller's stream (its pods), the context
-// stream when it wrote the table since (deltas, binds), and the slot's
-// previous collective (it read the keys this sweep overwrites).
-int prepare_locked(ms_ctx *c, uint32_t n, hipStream_t s, uint32_t &si, hipStream_t &X) {
+// The collective of batch b on the collective stream; then the batch is
+// pending, and the oldest are decoded when the ordering says so.
+int collective_locked(ms_ctx *c, const Batch &b, HostClock::time_point &tp) {
     CommState &m = *c->comm;
-    const uint32_t G = (uint32_t)m.world, per = cdiv(n, G);
-    si = (uint32_t)(m.submitted % (m.depth + 1));
-    const int xi = (int)(m.submitted & 1u);
-    X = m.two_streams ? m.ss[xi].get() : s;
-    ShardSlot &sl = m.slot[si];
-    int rc = slot_ensure(c, sl, per);
-    if (rc) return rc;
-    if (X != s) {
-        MS_HIP(c, hipEventRecord(m.ev_in, s));
-        MS_HIP(c, hipStreamWaitEvent(X, m.ev_in, 0));
-    }
-    if (m.ctx_seen != c->order.seq() || m.ctx_seen_stream != s) {
-        MS_HIP(c, hipEventRecord(m.ev_ctx, c->stream));
-        MS_HIP(c, hipStreamWaitEvent(X, m.ev_ctx, 0));
-        if (m.two_streams) MS_HIP(c, hipStreamWaitEvent(m.ss[xi ^ 1], m.ev_ctx, 0));
-        m.ctx_seen = c->order.seq();
-        m.ctx_seen_stream = s;
-    }
-    // the slot's previous collective (submission k - depth - 1) read the keys
-    // this sweep overwrites. Collectives complete in issue order, so one wait
-    // covers all older ones: wait for submission k - L's and skip the next
-    // waits it covers. L = 2 (two steps old, normally done, and never the one
-    // the previous sweep feeds); with coalesced submits L = 3: k is the first
-    // of a pair (then k - 1 and k - 2 are the previous pair, whose collectives
-    // follow the previous launch) or k - 3's wait is already on X.
-    if (sl.used) {
-        const uint64_t k = m.submitted, prev = k - (m.depth + 1);
-        const uint32_t L = coalescable(c) ? 3u : 2u;
-        if (m.two_streams || m.depth + 1 <= L) {
-            MS_HIP(c, hipStreamWaitEvent(X, m.ev_comb[si], 0));
-        } else if (m.x_stream != X || m.x_comb_seen <= prev) {
-            m.x_stream = X;
-            MS_HIP(c, hipStreamWaitEvent(X, m.ev_comb[(k - L) % (m.depth + 1)], 0));
-            m.x_comb_seen = k - L + 1;
-        }
-    }
-    ++m.submitted;
-    return MS_OK;
-}
-
-// The collective of slot si's batch on the collective stream, after the sweep
-// event ev (that recorded the batch's sweep) and the drain that decoded the
-// slot's previous batch; then the batch joins the pending list (and the oldest
-// are decoded once more than `depth` wait).
-int collective_locked(ms_ctx *c, uint32_t si, hipEvent_t ev, uint32_t n, const ms_pod_rec *pods, ms_result *results,
-                      HostClock::time_point &tp) {
-    CommState &m = *c->comm;
-    ShardSlot &sl = m.slot[si];
-    const uint32_t G = (uint32_t)m.world, per = cdiv(n, G);
+    ShardSlot &sl = m.slot[b.slot];
+    const uint32_t G = (uint32_t)m.world, per = cdiv(b.n, G);
     const int ps = c->cfg.plugin_set;
-    // one wait covers a whole drain
-    if (ev) MS_HIP(c, hipStreamWaitEvent(m.cs, ev, 0));
-    if (sl.used && sl.dec_gen > m.cs_drain_seen) {
-        MS_HIP(c, hipStreamWaitEvent(m.cs, m.ev_drained, 0));
-        m.cs_drain_seen = m.drains;
-    }
-    sl.used = true;
+    MS_ORD(c, m.order.before_collective(b.slot));
     host_tick(m, 2, tp);  // events to the collective stream
     ncclResult_t r = ncclSuccess;
     if (ps == MS_PLUGINS_NU_NN || ps == MS_PLUGINS_NU_TT_NN) {  // the keys alone: one call
@@ -343,12 +294,10 @@ int collective_locked(ms_ctx *c, uint32_t si, hipEvent_t ev, uint32_t n, const m
     }
     if (r != ncclSuccess) return fail(c, MS_E_RCCL, std::string("sharded combine: ") + CCL(ncclGetErrorString)(r));
     host_tick(m, 3, tp);  // the grouped reduce-scatter
-    MS_HIP(c, hipEventRecord(m.ev_comb[si], m.cs));
-    Pending p{si, n, 0, 0, pods, results};
-    slice_of(m, n, p.first, p.count);
-    m.pending.push_back(p);
-    int rc = MS_OK;
-    if (m.pending.size() > m.depth) rc = drain_locked(c, std::min<size_t>(m.group, m.pending.size()));
+    size_t n_drain = 0;
+    MS_ORD(c, m.order.after_collective(b.slot, n_drain));
+    m.pending.push_back(b);
+    const int rc = n_drain ? drain_locked(c, n_drain) : MS_OK;
     host_tick(m, 4, tp);  // bookkeeping + drains
     return rc;
 }
@@ -356,46 +305,46 @@ int collective_locked(ms_ctx *c, uint32_t si, hipEvent_t ev, uint32_t n, const m
 // The stashed submission's sweep alone, then its collective.
 int flush_stash(ms_ctx *c) {
     CommState &m = *c->comm;
-    if (!m.stash.on) return MS_OK;
-    const CommState::Stash st = m.stash;
-    m.stash.on = false;
+    if (!m.order.held()) return MS_OK;
+    const Batch b = m.stash;
     HostClock::time_point tp = m.host_prof ? HostClock::now() : HostClock::time_point();
-    int rc = sweep_locked(c, st.n, st.pods, m.slot[st.si].keys, nullptr, st.X, m.ev_swept[st.si]);
+    MS_HIP(c, made(m.order.sweep_event(b.slot).ensure()));
+    int rc = sweep_locked(c, b.n, b.pods, m.slot[b.slot].keys, nullptr, b.X, m.order.sweep_event(b.slot));
     if (rc) return rc;
-    m.reads_outstanding = true;
-    return collective_locked(c, st.si, m.ev_swept[st.si], st.n, st.pods, st.results, tp);
+    MS_ORD(c, m.order.swept(b.slot, b.X, true));
+    return collective_locked(c, b, tp);
 }
 
 // MS_PLUGINS_NU_TT_NN, two-pass: the census of this shard on X, the all-gather of
 // every shard's on the collective stream, then the picks on X again (the table's
-// readers stay on the sweep stream, behind the delta fence ev_swept). The shared
-// two-pass scratch (d_tt) passes from sweep stream to sweep stream by ev_tt.
-int tt2_sharded_sweep(ms_ctx *c, uint32_t si, uint32_t n, const ms_pod_rec *pods, hipStream_t X) {
+// readers stay on the sweep stream, behind the delta fence). The shared two-pass
+// scratch (d_tt) passes from sweep stream to sweep stream (tt_take / tt_release).
+int tt2_sharded_sweep(ms_ctx *c, const Batch &b) {
     CommState &m = *c->comm;
-    ShardSlot &sl = m.slot[si];
-    const uint32_t seed32 = seed32_of(c->cfg.seed);
+    ShardSlot &sl = m.slot[b.slot];
+    const uint32_t si = b.slot, n = b.n, seed32 = seed32_of(c->cfg.seed);
+    const hipStream_t X = b.X;
     int rc = ensure_tt(c, tt2_scratch_bytes(c->rows_dev, std::max(1u, n)));
     if (rc) return rc;
-    MS_HIP(c, made(c->ev_tt.ensure()));
-    if (c->tt_stream && c->tt_stream != X) MS_HIP(c, hipStreamWaitEvent(X, c->ev_tt, 0));
-    MS_HIP(c, launch_tt2_planes(c->t, c->rows_dev, c->d_tt, X));
-    MS_HIP(c, launch_tt2_census_shard(c->t, c->rows_dev, pods, n, seed32, c->d_tt, std::max(1u, n), sl.cen_mine, X));
-    MS_HIP(c, hipEventRecord(m.ev_swept[si], X));
-    MS_HIP(c, hipStreamWaitEvent(m.cs, m.ev_swept[si], 0));
-    if (sl.used && sl.dec_gen > m.cs_drain_seen) {  // the slot's previous final read cen_all
-        MS_HIP(c, hipStreamWaitEvent(m.cs, m.ev_drained, 0));
-        m.cs_drain_seen = m.drains;
-    }
-    const ncclResult_t r = CCL(ncclAllGather)(sl.cen_mine, sl.cen_all, (size_t)n * MS_TT_CENSUS_BYTES, ncclUint8,
-                                              m.comm, m.cs);
-    if (r != ncclSuccess) return fail(c, MS_E_RCCL, std::string("TaintToleration census all-gather: ") +
-                                                        CCL(ncclGetErrorString)(r));
-    MS_HIP(c, hipEventRecord(m.ev_ag[si], m.cs));
-    MS_HIP(c, hipStreamWaitEvent(X, m.ev_ag[si], 0));
-    MS_HIP(c, launch_tt2_pick_shard(c->t, c->rows_dev, pods, n, seed32, c->d_tt, std::max(1u, n), sl.cen_all, n,
-                                    (uint32_t)m.world, (uint32_t)m.rank, sl.keys, X));
-    MS_HIP(c, hipEventRecord(c->ev_tt, X));
-    c->tt_stream = X;
+    rc = tt_take(c, X);
+    if (rc) return rc;
+    rc = [&]() -> int {
+        MS_HIP(c, launch_tt2_planes(c->t, c->rows_dev, c->d_tt, X));
+        MS_HIP(c, launch_tt2_census_shard(c->t, c->rows_dev, b.pods, n, seed32, c->d_tt, std::max(1u, n), sl.cen_mine, X));
+        MS_ORD(c, m.order.census_done(si, X));
+        const ncclResult_t r = CCL(ncclAllGather)(sl.cen_mine, sl.cen_all, (size_t)n * MS_TT_CENSUS_BYTES, ncclUint8,
+                                                  m.comm, m.cs);
+        if (r != ncclSuccess) return fail(c, MS_E_RCCL, std::string("TaintToleration census all-gather: ") +
+                                                            CCL(ncclGetErrorString)(r));
+        MS_ORD(c, m.order.gathered(si, X));
+        MS_HIP(c, launch_tt2_pick_shard(c->t, c->rows_dev, b.pods, n, seed32, c->d_tt, std::max(1u, n), sl.cen_all, n,
+                                        (uint32_t)m.world, (uint32_t)m.rank, sl.keys, X));
+        return MS_OK;
+    }();
+    // (after a failure too: the next cycle on another stream follows what this one enqueued)
+    const int released = tt_release(c, X);
+    if (rc || released) return rc ? rc : released;
+    MS_ORD(c, m.order.swept(si, X, false));  // (again: the fence and the reduce-scatter follow the picks)
     return MS_OK;
 }
 
@@ -408,12 +357,16 @@ int submit_locked(ms_ctx *c, uint32_t n, const ms_pod_rec *pods, ms_result *resu
         int rc = flush_stash(c);
         if (rc) return rc;
     }
-    uint32_t si = 0;
-    hipStream_t X = nullptr;
-    int rc = prepare_locked(c, n, s, si, X);
+    // the slot (its buffers sized for n pods) and the sweep stream, ordered
+    Batch b{m.order.next_slot(), n, 0, 0, pods, results, nullptr};
+    slice_of(m, n, b.first, b.count);
+    const uint32_t si = b.slot;
+    int rc = slot_ensure(c, si, cdiv(n, (uint32_t)m.world));
     if (rc) return rc;
+    MS_ORD(c, m.order.begin(s, c->order.seq(), co, b.X));
+    const hipStream_t X = b.X;
     host_tick(m, 0, tp);  // ordering of the sweep stream
-    if (co && (!m.stash.on || m.stash.X != X)) {
+    if (co && (!m.order.held() || m.stash.X != X)) {
         // Coalesced submits (MINISCHED_SHARD_COALESCE=0 turns it off): this
         // batch's sweep waits for the next submission (or a drain / table
         // writer) and then shares ONE K1 launch with it, so the launch's ramp
@@ -421,36 +374,37 @@ int submit_locked(ms_ctx *c, uint32_t n, const ms_pod_rec *pods, ms_result *resu
         // paid once per two batches. Its collective starts after both sweeps.
         rc = flush_stash(c);
         if (rc) return rc;
-        m.stash = CommState::Stash{true, n, si, pods, results, X};
+        m.stash = b;
+        m.order.hold(si);
         return MS_OK;
     }
     ShardSlot &sl = m.slot[si];
-    if (co) {  // the stashed batch and this one in one launch
-        const CommState::Stash st = m.stash;
-        m.stash.on = false;
-        MS_HIP(c, launch_sweep_pp2(c->t, c->d_cand, c->rows_dev, st.pods, st.n, m.slot[st.si].keys, pods, n, sl.keys,
-                                   seed32_of(c->cfg.seed), c->present_dev, c->num_cus, X, m.ev_swept[si]));
-        host_tick(m, 1, tp);  // the sweep launch
-        m.reads_outstanding = true;
-        rc = collective_locked(c, st.si, m.ev_swept[si], st.n, st.pods, st.results, tp);
-        if (rc) return rc;
-        return collective_locked(c, si, nullptr, n, pods, results, tp);  // (cs already waits for the sweep)
-    }
     const int ps = c->cfg.plugin_set;
-    // (ev_swept recorded by the sweep's own dispatch for K1: no separate event
-    // packet between consecutive sweeps on X)
+    // (the sweep event is recorded by the sweep's own dispatch for K1: no
+    // separate event packet between consecutive sweeps on X)
+    if (ps != MS_PLUGINS_NU_TT_NN) MS_HIP(c, made(m.order.sweep_event(si).ensure()));
+    if (co) {  // the stashed batch and this one in one launch
+        const Batch b0 = m.stash;
+        MS_HIP(c, launch_sweep_pp2(c->t, c->d_cand, c->rows_dev, b0.pods, b0.n, m.slot[b0.slot].keys, pods, n, sl.keys,
+                                   seed32_of(c->cfg.seed), c->present_dev, c->num_cus, X, m.order.sweep_event(si)));
+        host_tick(m, 1, tp);  // the sweep launch
+        MS_ORD(c, m.order.swept_pair(b0.slot, si));
+        rc = collective_locked(c, b0, tp);
+        if (rc) return rc;
+        return collective_locked(c, b, tp);
+    }
     if (ps == MS_PLUGINS_NU_TT_NN) {
         // the two-pass form: this shard's census, every shard's by one all-gather,
         // then this shard's picks for every pod (keys, combined by the reduce-scatter)
-        rc = tt2_sharded_sweep(c, si, n, pods, X);
-        if (rc == MS_OK && hipEventRecord(m.ev_swept[si], X) != hipSuccess) rc = fail(c, MS_E_HIP, "event record");
+        rc = tt2_sharded_sweep(c, b);
+        if (rc) return rc;
     } else {
-        rc = sweep_locked(c, n, pods, sl.keys, ps == MS_PLUGINS_NU_NN ? nullptr : sl.flags, X, m.ev_swept[si]);
+        rc = sweep_locked(c, n, pods, sl.keys, ps == MS_PLUGINS_NU_NN ? nullptr : sl.flags, X, m.order.sweep_event(si));
+        if (rc) return rc;
+        MS_ORD(c, m.order.swept(si, X, true));
     }
-    if (rc) return rc;
     host_tick(m, 1, tp);  // the sweep launch
-    m.reads_outstanding = true;
-    return collective_locked(c, si, m.ev_swept[si], n, pods, results, tp);
+    return collective_locked(c, b, tp);
 }
 
 // Sequential-window buffers for windows of w pods.
@@ -540,18 +494,12 @@ void comm_rank_world(const ms_ctx *c, int32_t *rank, int32_t *world) {
 }
 
 int comm_fence_reads(ms_ctx *c, hipStream_t writer) {
-    CommState *m = c->comm;
-    if (m && m->stash.on) {  // the stashed batch's sweep reads the table before this writer
-        const int rc = flush_stash(c);
-        if (rc) return rc;
-    }
-    if (!m || !m->reads_outstanding) return 0;
-    // every sweep in flight is the newest of its slot (a slot is swept again only
-    // after the collective that read its previous sweep): wait for each slot's
-    for (uint32_t i = 0; i < kPipeMax; ++i)
-        if (m->slot[i].used) MS_HIP(c, hipStreamWaitEvent(writer, m->ev_swept[i], 0));
-    m->reads_outstanding = false;
-    return 1;
+    if (!c->comm) return 0;
+    const int rc = flush_stash(c);  // the stashed batch's sweep reads the table before this writer
+    if (rc) return rc;
+    const int fenced = c->comm->order.fence(writer);
+    if (fenced < 0) return fail(c, MS_E_HIP, std::string("stream ordering (fence): ") + hipGetErrorString(hipGetLastError()));
+    return fenced;
 }
 
 void comm_free(ms_ctx *c) {
@@ -611,7 +559,8 @@ int comm_schedule_device(ms_ctx *c, uint32_t n, const ms_pod_rec *pods_dev, ms_r
 
 namespace {
 
-// The communicator's streams and events, then the rendezvous of the ranks.
+// The communicator's streams (the ordering class makes its events as it first
+// records them), then the rendezvous of the ranks.
 int comm_setup(ms_ctx *c, CommState &m, const ms_comm_id *id, int32_t rank, int32_t world) {
     // The collective and decode streams get the highest priority: high-priority
     // streams are served by hardware queues of their own, so the caller's
@@ -624,18 +573,10 @@ int comm_setup(ms_ctx *c, CommState &m, const ms_comm_id *id, int32_t rank, int3
     MS_HIP(c, made(m.cs.ensure(hipStreamNonBlocking, cprio)));
     // (MINISCHED_SHARD_STREAMS=2 only) two sweep streams at normal priority (at the
     // highest, the collectives fell behind)
-    if (m.two_streams)
+    if (m.order.two_streams())
         for (Stream &q : m.ss) MS_HIP(c, made(q.ensure(hipStreamNonBlocking, 0)));
     MS_HIP(c, made(m.ds.ensure(hipStreamNonBlocking, cprio)));
-    MS_HIP(c, made(m.ev_ds.ensure()));
-    for (uint32_t i = 0; i < kPipeMax; ++i) {
-        MS_HIP(c, made(m.ev_swept[i].ensure()));
-        MS_HIP(c, made(m.ev_comb[i].ensure()));
-        MS_HIP(c, made(m.ev_ag[i].ensure()));
-    }
-    MS_HIP(c, made(m.ev_drained.ensure()));
-    MS_HIP(c, made(m.ev_in.ensure()));
-    MS_HIP(c, made(m.ev_ctx.ensure()));
+    m.order.attach(c->stream, m.cs, m.ds, m.ss[0], m.ss[1]);
     ncclUniqueId uid;
     std::memcpy(&uid, id->internal, sizeof(uid));
     const ncclResult_t r = CCL(ncclCommInitRank)(&m.comm, world, uid, rank);
@@ -668,13 +609,12 @@ int ms_comm_init(ms_ctx *c, const ms_comm_id *id, int32_t rank, int32_t world) {
     std::lock_guard<std::mutex> g(c->sched_mu);
     if (c->comm) return fail(c, MS_E_INVAL, "ms_comm_init: the context already has a communicator");
     MS_HIP(c, hipSetDevice(c->cfg.device));
-    CommState *m = new (std::nothrow) CommState();
+    bool two_streams = false;
+    if (const char *e = getenv("MINISCHED_SHARD_STREAMS")) two_streams = atoi(e) == 2;
+    CommState *m = new (std::nothrow) CommState(4, two_streams);  // (depth + 1 <= kPipeMax buffer sets)
     if (!m) return fail(c, MS_E_OOM, "ms_comm_init: host allocation");
     m->rank = rank;
     m->world = world;
-    m->depth = std::min<uint32_t>(m->depth, kPipeMax - 1);
-    m->group = m->depth;
-    if (const char *e = getenv("MINISCHED_SHARD_STREAMS")) m->two_streams = atoi(e) == 2;
     if (const char *e = getenv("MINISCHED_HOST_PROF")) m->host_prof = atoi(e) == 1;
     if (const char *e = getenv("MINISCHED_SHARD_COALESCE")) m->coalesce = atoi(e) != 0;
     // Attached before the streams exist (MS_HIP reports through the context);

@@ -292,6 +292,11 @@ int tt_cycle_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, void *
 // MS_PLUGINS_NU_TT_NN scratch of at least `need` bytes (the two-pass bit-sliced
 // cycle's, or the node shards' summaries).
 int ensure_tt(ms_ctx *c, size_t need);
+// d_tt is one scratch for every TT cycle of the context (ev_tt above): a cycle
+// on s takes it before its first launch (s waits for the previous cycle's end
+// when that ran on another stream) and releases it after its last.
+int tt_take(ms_ctx *c, hipStream_t s);
+int tt_release(ms_ctx *c, hipStream_t s);
 
 // ms_seq_host.cpp: the sequential engine's host side
 int ensure_tiles(ms_ctx *c, uint32_t n_tiles);

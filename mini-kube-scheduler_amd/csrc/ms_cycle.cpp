@@ -27,13 +27,13 @@ int ensure_tt(ms_ctx *c, size_t need) {
 
 // d_tt is one scratch for every TT cycle of the context (ms_ctx.h ev_tt): a
 // cycle on another stream than the previous one waits for that one's end.
-static int tt_take(ms_ctx *c, hipStream_t s) {
+int tt_take(ms_ctx *c, hipStream_t s) {
     MS_HIP(c, made(c->ev_tt.ensure()));
     if (c->tt_stream && c->tt_stream != s) MS_HIP(c, hipStreamWaitEvent(s, c->ev_tt, 0));
     return MS_OK;
 }
 
-static int tt_release(ms_ctx *c, hipStream_t s) {
+int tt_release(ms_ctx *c, hipStream_t s) {
     MS_HIP(c, hipEventRecord(c->ev_tt, s));
     c->tt_stream = s;
     return MS_OK;

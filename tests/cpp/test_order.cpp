@@ -1,8 +1,6 @@
 // The cross-stream ordering protocol of a context
-// (mini-kube-scheduler_amd/csrc/ms_order.h) over a model of streams and events.
-// Streams are small integers, every enqueued piece of work gets an id, and a
-// stream carries the set of ids that happen before its tail: record snapshots
-// that set into the event, wait unions the snapshot into the stream. The
+// (mini-kube-scheduler_amd/csrc/ms_order.h) over the model of streams and
+// events in order_model.h (happens-before sets per stream). The
 // driver uses the class the way the library's call guard does (enter, one
 // piece of work on the stream, leave), with flushes and binds on the context
 // stream between calls and fences reported or not, and checks
@@ -19,92 +17,22 @@
 #include <vector>
 
 #include "ms_order.h"
+#include "order_model.h"
 
 using namespace msgpu;
 
 namespace {
 
-template <int N>
-struct Bits {
-    uint64_t w[N] = {};
-    void set(int i) { w[i >> 6] |= 1ull << (i & 63); }
-    void merge(const Bits &o) {
-        for (int k = 0; k < N; ++k) w[k] |= o.w[k];
-    }
-    bool holds(const Bits &o) const {
-        for (int k = 0; k < N; ++k)
-            if (o.w[k] & ~w[k]) return false;
-        return true;
-    }
-};
-
 constexpr int kCtx = 0, kA = 1, kB = 2, kStreams = 3;
 
 template <int N>
-struct ModelEvent {
-    bool made = false;  // created lazily, by the first record
-    Bits<N> snap;
-};
-
-// The device as the protocol sees it, and what the checks count.
+using World = order_model::World<N, kStreams>;
 template <int N>
-struct World {
-    Bits<N> hb[kStreams];  // per stream: the work that happens before its tail
-    Bits<N> ordered;       // every ordered piece of work enqueued so far
-    int next_id = 0;
-    long records = 0, waits = 0, events_made = 0;
-    bool violated = false, bad_wait = false;
-    long fail_in = 0;  // the k-th record / wait from now fails (1 = the next one); 0 = none
-
-    // A piece of ordered work on stream s: checked, then part of the order.
-    void work(int s) {
-        if (!hb[s].holds(ordered)) violated = true;
-        const int id = next_id++;
-        hb[s].set(id);
-        ordered.set(id);
-    }
-    // comm_fence_reads inserted waits: the context stream now follows a table
-    // reader on another stream, and so must everything ordered after it.
-    void fence() {
-        const int id = next_id++;
-        hb[kCtx].set(id);
-        ordered.set(id);
-    }
-};
-
-// The policy is stateless, like the library's: it reaches the world of the
-// run being stepped through one slot (Sim::step sets it), so a run, world and
-// rule together, can be copied when the search branches.
+using ModelPolicy = order_model::ModelPolicy<N, kStreams>;
 template <int N>
 World<N> *&world() {
-    static World<N> *p = nullptr;
-    return p;
+    return order_model::world<N, kStreams>();
 }
-
-template <int N>
-struct ModelPolicy {
-    using stream = int;
-    using event = ModelEvent<N>;
-    static bool record(event &e, int s) {
-        World<N> *w = world<N>();
-        if (w->fail_in && --w->fail_in == 0) return false;
-        if (!e.made) {
-            e.made = true;
-            ++w->events_made;
-        }
-        e.snap = w->hb[s];
-        ++w->records;
-        return true;
-    }
-    static bool wait(int s, event &e) {
-        World<N> *w = world<N>();
-        if (w->fail_in && --w->fail_in == 0) return false;
-        if (!e.made) w->bad_wait = true;  // (a wait for an event never recorded orders nothing)
-        w->hb[s].merge(e.snap);
-        ++w->waits;
-        return true;
-    }
-};
 
 // The rule before ms_order.h, from the parent revision's order_after_ctx_stream
 // (enter) and chain_back (leave): a call on the context stream moves no counter.

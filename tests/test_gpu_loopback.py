@@ -212,6 +212,56 @@ def test_loopback_tt_distinct_batches_concurrent_streams(lb, oracle, monkeypatch
             _same(res[k], o, nb * k + first, nb * k + first + count, f"TT {mode} rank {r} batch {k}")
 
 
+@pytest.mark.parametrize("mode", ["one_caller_stream", "alternating_caller_streams", "two_sweep_streams"])
+@pytest.mark.parametrize("plugin_set", [0, 3])
+def test_loopback_slot_reuse_distinct_batches(lb, oracle, monkeypatch, plugin_set, mode):
+    # Two full rounds of slot reuse at world 2 (12 submits, depth 4) with every batch distinct and
+    # in its own result buffer, and two node deltas on the way (tests/_shard_seq.py); no host
+    # synchronisation of the caller streams before the final drains. Every rank's slice of every
+    # batch equals the oracle over the whole cluster for the table in force at its submit
+    import torch
+
+    import _shard_seq
+
+    if mode == "two_sweep_streams":
+        monkeypatch.setenv("MINISCHED_SHARD_STREAMS", "2")
+    G, seed = 2, 900 + plugin_set
+    tables, batches, want = _shard_seq.expected(oracle, plugin_set, seed)
+    cuts = _cuts(_shard_seq.N_NODES, G)
+    cid = _lib.comm_id_create(lb)
+    dev = torch.device("cuda:0")
+
+    def rank_fn(r):
+        lo, hi = cuts[r]
+        e = _joined(lb, cid, r, G, tables[0], lo, hi, plugin_set, seed)
+        try:
+            slices = [e.sharded_slice(len(p)) for p in batches]
+            pods = [torch.from_numpy(p.view(np.uint8).copy()).to(dev) for p in batches]
+            res = [torch.full((max(1, count) * 24,), 0xAB, dtype=torch.uint8, device=dev) for _, count in slices]
+            torch.cuda.synchronize()
+            ss = [torch.cuda.Stream(device=dev) for _ in range(2)]
+            for i in range(len(batches)):
+                if i in _shard_seq.DELTA_BEFORE:
+                    e.upsert(np.arange(lo, hi), tables[1 + _shard_seq.DELTA_BEFORE.index(i)][lo:hi])
+                    e.flush()
+                s = ss[i % 2] if mode == "alternating_caller_streams" else ss[0]
+                e.sharded_submit(len(batches[i]), pods[i].data_ptr(), res[i].data_ptr(), s.cuda_stream)
+            for s in ss:
+                e.sharded_drain(s.cuda_stream)
+            torch.cuda.synchronize()
+            return [(first, count, x.cpu().numpy().view(_lib.RESULT)[:count].copy())
+                    for (first, count), x in zip(slices, res)]
+        finally:
+            e.close()
+
+    got = run_ranks(G, rank_fn)
+    for i in range(len(batches)):
+        for r in range(G):
+            first, count, res = got[r][i]
+            _same(res, want[i], first, first + count, f"set {plugin_set} {mode} rank {r} batch {i}")
+        assert sum(got[r][i][1] for r in range(G)) == len(batches[i])
+
+
 @pytest.mark.parametrize("G", [2, 4, 8])
 def test_loopback_config_c_full(lb, oracle, G):
     # config C at full size (100k nodes x 100k pods) through the library's pipelined

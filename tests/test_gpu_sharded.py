@@ -402,6 +402,42 @@ def test_library_submit_coalescing(oracle, monkeypatch, capfd, coalesce, words, 
         assert "MS_HOST_PROF submits=5 " in capfd.readouterr().err
 
 
+@pytest.mark.parametrize("plugin_set,coalesce", [(0, "1"), (0, "0"), (1, "1"), (2, "1"), (3, "1")])
+def test_library_slot_reuse_distinct_batches(oracle, monkeypatch, plugin_set, coalesce):
+    # Two full rounds of slot reuse (12 submits, depth 4) with every batch distinct and in its
+    # own result buffer, and two node deltas on the way (tests/_shard_seq.py): one caller stream,
+    # no host synchronisation of it before the final drain. Every batch equals the oracle for the
+    # table in force at its submit (csrc/ms_shard_order.h: the slot's keys, reduced keys and the
+    # fence; neighbouring and slot-sharing batches have different results)
+    import torch
+
+    import _shard_seq
+    from minisched_amd import _lib
+
+    monkeypatch.setenv("MINISCHED_SHARD_COALESCE", coalesce)
+    seed = 900 + plugin_set
+    tables, batches, want = _shard_seq.expected(oracle, plugin_set, seed)
+    dev = torch.device("cuda:0")
+    e = _comm_engine(tables[0], plugin_set, seed)
+    try:
+        s = torch.cuda.Stream(device=dev)
+        pods = [torch.from_numpy(p.view(np.uint8).copy()).to(dev) for p in batches]
+        res = [torch.full((len(p) * _lib.RESULT.itemsize,), 0xAB, dtype=torch.uint8, device=dev) for p in batches]
+        torch.cuda.synchronize()
+        for i in range(len(batches)):
+            if i in _shard_seq.DELTA_BEFORE:
+                e.upsert(np.arange(_shard_seq.N_NODES), tables[1 + _shard_seq.DELTA_BEFORE.index(i)])
+                e.flush()
+            e.sharded_submit(len(batches[i]), pods[i].data_ptr(), res[i].data_ptr(), s.cuda_stream)
+        e.sharded_drain(s.cuda_stream)
+        s.synchronize()
+        got = [r.cpu().numpy().view(_lib.RESULT) for r in res]
+    finally:
+        e.close()
+    for i in range(len(batches)):
+        _same(got[i], want[i], 0, len(batches[i]), f"set {plugin_set} batch {i}")
+
+
 def test_library_schedule_batch_1rank(oracle):
     # ms_schedule_batch on a communicator: every pod's result on every rank (all-gather of
     # the slices), binds committed on the rank's own shard; NU+NN batched and sequential,

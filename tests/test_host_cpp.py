@@ -170,6 +170,27 @@ def test_stream_order_model_asan(tmp_path):
     assert int(lines[1].split()[6]) == 4000, out  # "random sequences of length 50 checked: N"
 
 
+def test_shard_order_model_asan(tmp_path):
+    # the node-sharded pipeline's ordering (csrc/ms_shard_order.h, the copy ms_comm.cpp instantiates with
+    # the HIP calls) over the same model, driven as ms_comm.cpp drives it: every access to the table, a
+    # batch's pods and results, a slot's buffers and d_tt follows every earlier conflicting one, in all
+    # sequences of submits, drains, table writes and regrows up to length 7 in every setting (combine
+    # kind, one or two sweep streams, coalescing, depths 1 to 7) and in seeded random ones of 40
+    # submissions, with as many records and waits as the rule it replaced wherever that rule held; the
+    # slot regrown while its batch is pending, which that rule missed, is a named case the model must see fail
+    exe = str(tmp_path / "test_shard_order")
+    src = os.path.join(ROOT, "tests", "cpp", "test_shard_order.cpp")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+                    "-I", os.path.join(PKG, "csrc"), src, "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = _run([exe], env=env)
+    print(out)
+    lines = out.splitlines()
+    assert lines[-1] == "0 failed", out
+    assert lines[0].startswith("sequences up to length 7 checked: 16460178 in 49 settings"), out
+    assert lines[1].startswith("random sequences of 40 submissions checked: 1960 "), out
+
+
 def test_nam_layout_plan_asan(tmp_path):
     # the NodeAffinity scratch plan (csrc/ms_nam_layout.h, the copy ms_affinity.hip and ms_cycle.cpp
     # use): every chunk of a call, the short last one included, fits the call's allocation; and the
