@@ -104,7 +104,7 @@ struct ms_ctx {
     NodeTable t{};  // raw views: its columns point into d_table, t.planes is d_planes
     DevBuf<void> d_table;  // the node table's columns, one allocation (ms_create)
     DevBuf<uint32_t> d_planes;
-    DevBuf<uint32_t> d_cand;  // K1 pp's per-class candidate lists (ms_internal.h cand_words), rebuilt with the planes
+    DevBuf<uint32_t> d_cand;  // K1 pp's candidate lists S_d / U_d (ms_internal.h cand_words), rebuilt with the planes
     ~ms_ctx();  // device set, communicator freed, both streams drained; then the members (ms_capi.cpp)
 
     // helper threads for the host copies of single-shard host-array calls

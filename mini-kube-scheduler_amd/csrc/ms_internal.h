@@ -100,21 +100,29 @@ enum : uint32_t {
 };
 
 // K1 "pp" candidate lists, derived from the planes (k_build_cand after every
-// k_build_planes): for each of the 20 classes c = name digit + 10 * tolerates
-// the hash bases (base + row) * kG24 of the rows a pod of the class can win,
-// i.e. the present rows whose name ends in the digit and that are schedulable
-// or tolerated, in row order. One u32 buffer (the context's d_cand):
-//   [c], c <= 20     first entry of list c; [c + 1] - [c] is its padded length
-//   [21 + c]         its real length (0: no candidate, the list is empty)
+// k_build_planes): two lists per name digit d of the hash bases (base + row) *
+// kG24 of the present rows whose name ends in d, in row order: S_d (list d) the
+// schedulable ones, U_d (list 10 + d) the unschedulable (cordoned) ones. A pod
+// of digit d that does not tolerate node.kubernetes.io/unschedulable can win
+// exactly the rows of S_d, one that tolerates it those of S_d and U_d. The two
+// lists of a digit lie next to each other, S_d's tiles then U_d's, so a sweep
+// loads them as one run of tiles and stops short of U_d for the pods that do
+// not tolerate. One u32 buffer (the context's d_cand):
+//   [d], d <= 10     first entry of S_d; [d + 1] - [d] is the padded length of
+//                    S_d and U_d together (0: no present row ends in d)
+//   [11 + d]         tiles of S_d (0: S_d is empty); U_d's follow them
+//   [21 + c]         real length of list c (c = d: S_d, c = 10 + d: U_d)
 //   [kCandHeader ..] the entries; every list padded to a multiple of kCandTile
-//                    with copies of its first entry (a duplicate candidate
+//                    with copies of its own first entry (a duplicate candidate
 //                    leaves every pod's maximum unchanged)
-// A row is in at most two lists, so cand_words(cap) words hold any table.
+// A row is in at most one list and a list's padding is less than a tile, so
+// cand_words(cap) words hold any table.
 constexpr uint32_t kCandClasses = 20;
+constexpr uint32_t kCandDigits = kCandClasses / 2u;
 constexpr uint32_t kCandTile = 192;   // entries per tile: 3 per lane of a wave
 constexpr uint32_t kCandHeader = 64;  // words before the entries
 __host__ __device__ inline size_t cand_words(uint32_t cap) {
-    return (size_t)kCandHeader + 2u * (size_t)cap + kCandClasses * kCandTile;
+    return (size_t)kCandHeader + (size_t)cap + kCandClasses * kCandTile;
 }
 
 // One queued node delta (upsert or delete) as it travels to the device.

@@ -38,10 +38,18 @@
 // costs one add and one mix32 per candidate, 17 VALU per pod and group.
 // Candidate lists (sweep_lists): the candidate rows of a class depend only on
 // the node table, so k_build_cand lists them once per flush, beside the planes
-// (ms_internal.h kCand*). Where one workgroup holds every row (grid.y == 1) a
-// sorted chunk's digit classes are swept over the class's dense list, 192
-// entries to a wave and tile, whatever the rows' layout; the planes then serve
-// only pods without a digit and classes with no candidate.
+// (ms_internal.h kCand*): per name digit d the present schedulable rows (S_d)
+// and, right after them, the present cordoned rows (U_d). A pod of digit d that
+// does not tolerate node.kubernetes.io/unschedulable can win exactly the rows
+// of S_d, one that tolerates it those of S_d and U_d, so a row is listed once.
+// Where one workgroup holds every row (grid.y == 1) a sorted chunk's pods lie
+// digit by digit, the tolerating ones last, and a wave loads its tiles of a
+// digit (192 entries to a wave and tile) in one round, whatever the rows'
+// layout, sweeps the pods that do not tolerate through its S tiles and the
+// others through all of them; the planes then serve only pods without a digit
+// and pods with no candidate. What a wave needs to know of the chunk's 21
+// classes it gathers once, a class to a lane (class_lanes), so that moving on
+// to the next digit waits for nothing but the tiles.
 //
 // Grid: a workgroup holds ALL of the context's rows (up to 16 waves x 64 lanes
 // x kPpWords groups = 122,880 rows; more rows split over grid.y and combine
@@ -250,7 +258,9 @@ __device__ __forceinline__ uint2 pod_entry(const ms_pod_rec *__restrict__ pods, 
 }
 
 // Class runs. A pod's class is (fixed slot p0, tolerates): 20 digit classes,
-// key p0 + 10 * tolerates, and one "other" class (non-digit names). The match
+// key 2 * p0 + tolerates (slot-major: the pods of one slot, which is one name
+// digit, are contiguous, those that do not tolerate first, as the list form
+// sweeps them), and one "other" class (non-digit names). The match
 // mask of a word and the three candidate rows depend on the class alone, so
 // the prologue counting-sorts the chunk's entries by class and the sweep
 // hoists that work out of the pod loop for runs of one class (run_setup).
@@ -262,7 +272,8 @@ __device__ __forceinline__ uint2 pod_entry(const ms_pod_rec *__restrict__ pods, 
 // Bits 21-31 of an entry's y carry its index in the chunk (np <= kPpMaxChunk
 // = 2048), which the epilogue writes by.
 constexpr uint32_t kPpClasses = 20;
-// LDS words after pinfo: counts, rb, region B cursors, the candidate lists' 21 offsets (24 each)
+// LDS words after pinfo: counts, rb, region B cursors, the candidate lists' header (11 first
+// entries and 10 tile counts) (24 each)
 constexpr uint32_t kPpSortWords = 96;
 // Chunks below this are swept in arrival order (no sort, one region B): their
 // runs are too short for the run form (20 classes), and the small shards'
@@ -271,7 +282,7 @@ constexpr uint32_t kPpSortMin = 80;
 
 __device__ __forceinline__ uint32_t pod_class(uint32_t info) {
     const uint32_t p0 = (info >> 16) & 31u;
-    return p0 < 10u ? p0 + ((info & 16u) ? 10u : 0u) : kPpClasses;
+    return p0 < 10u ? 2u * p0 + ((info >> 4) & 1u) : kPpClasses;
 }
 
 // Candidate bases of one class for a wave whose NW words hold at most 3 rows
@@ -407,21 +418,68 @@ __device__ __forceinline__ void sweep_pods(const Word (&W)[KW], const Word &Wt, 
     }
 }
 
-// The list form. Tiles (kCandTile entries, 3 per lane) of the list of the class
-// whose pods carry class bits info: their count, and with off the list's first
-// entry; 0 for a class with no candidate. hdr: the buffer's header (in LDS).
-__device__ __forceinline__ uint32_t list_tiles(const uint32_t *hdr, uint32_t info, uint32_t *off) {
-    const uint32_t y = (uint32_t)__builtin_amdgcn_readfirstlane((int)info);
-    const uint32_t lc = (y & 15u) + ((y & 16u) ? kCandClasses / 2u : 0u);  // digit + 10 * tolerates
-    const uint32_t o = (uint32_t)__builtin_amdgcn_readfirstlane((int)hdr[lc]);
-    if (off) *off = o;
-    return ((uint32_t)__builtin_amdgcn_readfirstlane((int)hdr[lc + 1]) - o) / kCandTile;
+// The list form. The lists of name digit d as tiles of kCandTile entries, 3 per
+// lane: S_d's ns tiles from entry off, then U_d's, nt tiles in all
+// (ms_internal.h kCand*). hdr: the buffer's header (in LDS).
+struct DigitLists {
+    uint32_t off, ns, nt;
+};
+
+__device__ __forceinline__ DigitLists digit_lists(const uint32_t *hdr, uint32_t d) {
+    DigitLists L;
+    L.off = hdr[d];
+    L.nt = (hdr[d + 1] - L.off) / kCandTile;
+    L.ns = hdr[kCandDigits + 1u + d];
+    return L;
+}
+
+// Who is swept over what, for sweep_lists and sweep_range alike: the leading
+// tiles of its digit's lists that hold the candidates of a digit pod, S_d's for
+// a pod that does not tolerate, all of them for one that does. 0: the list form
+// has nothing for the pod and sweep_range takes it through the planes per pod:
+// a pod that does not tolerate when S_d is empty, one that does when S_d and
+// U_d both are (and the pods of the other class, which have no lists).
+__device__ __forceinline__ uint32_t list_tiles(const DigitLists &L, bool tolerates) {
+    return tolerates ? L.nt : L.ns;
+}
+
+// A list-form chunk's classes, class c in lane c (c <= kPpClasses; the lanes
+// above repeat the other class): its pods [beg, end) and the lists of its
+// digit, which is its sort slot c / 2 moved back by the table's base (pod_entry).
+// A wave gathers them twice, at the start of sweep_range and of sweep_lists,
+// every LDS read independent of the others, and takes a class's values by
+// v_readlane: read from LDS class by class, bounds, then an entry's digit, then
+// the header, they were three dependent round trips at each of 21 classes
+// before a wave hashed anything, and again at every digit of sweep_lists.
+// planes (wave-uniform): the classes with pods that sweep_range takes per pod,
+// one bit per class (the ballot counts lanes 0 .. kPpClasses only: the lanes
+// above hold copies of the other class, which must be swept once).
+struct ClassLanes {
+    uint32_t beg, end;
+    DigitLists L;
+    u64 planes;
+};
+
+__device__ __forceinline__ ClassLanes class_lanes(const uint32_t *hdr, const uint32_t *rb, uint32_t base10,
+                                                  uint32_t lane) {
+    const uint32_t c = min(lane, kPpClasses);
+    ClassLanes C;
+    C.beg = rb[c];
+    C.end = rb[c + 1];
+    C.L = digit_lists(hdr, ((c >> 1) + base10) % kCandDigits);
+    C.planes = __ballot(lane <= kPpClasses && C.beg < C.end &&
+                        (c == kPpClasses || list_tiles(C.L, (c & 1u) != 0u) == 0u));
+    return C;
+}
+
+__device__ __forceinline__ uint32_t lane_value(uint32_t v, uint32_t l) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
 }
 
 // One wave sweeps the pods [beg, end) of one class through NT tiles of the
-// class's list, B[3k .. 3k+2] the lane's entries of tile k: one add and one
-// mix32 per pod and entry. Every entry is a candidate of every pod of the
-// class (or a copy of one), so the maximum stands as it is, also when it is 0:
+// lists of the class's digit, B[3k .. 3k+2] the lane's entries of tile k: one
+// add and one mix32 per pod and entry. Every entry is a candidate of every pod
+// of the range (or a copy of one), so the maximum stands as it is, also when it is 0:
 // that is the hash of a real candidate then, and no redo is needed.
 // The range may start anywhere and its last block hold fewer than 8 pods,
 // whose absent pods are not hashed (wave-uniform tests).
@@ -460,35 +518,60 @@ __device__ __forceinline__ void sweep_list_pods(const uint32_t (&B)[3 * kPpWords
     }
 }
 
-// One wave's share of a class-sorted chunk in the list form: of every digit
-// class with candidates, wave wv takes tiles wv, wv + waves, .. of the class's
-// list, up to kPpWords of them per pass over the class's pods (a list of more
-// than kPpWords * waves tiles takes further passes; the waves combine by
-// atomicMax on LDS either way). A wave with no tile of a class skips it.
-__device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, const uint32_t *hdr,
-                                            const uint2 *pinfo, const uint32_t *rb, uint32_t wv, uint32_t waves,
-                                            uint32_t lane, u64 *lds) {
-    for (uint32_t c = 0; c < kPpClasses; ++c) {
-        const uint32_t beg = (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c]);
-        const uint32_t end = (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c + 1]);
-        if (beg >= end) continue;
-        uint32_t off;
-        const uint32_t ntile = list_tiles(hdr, pinfo[beg].y, &off);
+// (sweep_list_pods over the first n of the lane's tiles)
+__device__ __forceinline__ void sweep_list_tiles(uint32_t n, const uint32_t (&B)[3 * kPpWords], const uint2 *pinfo,
+                                                 uint32_t beg, uint32_t end, uint32_t lane, u64 *lds) {
+    switch (n) {  // wave-uniform
+        case 1: sweep_list_pods<1>(B, pinfo, beg, end, lane, lds); break;
+        case 2: sweep_list_pods<2>(B, pinfo, beg, end, lane, lds); break;
+        case 3: sweep_list_pods<3>(B, pinfo, beg, end, lane, lds); break;
+        default: sweep_list_pods<4>(B, pinfo, beg, end, lane, lds); break;
+    }
+}
+
+// The wave's tiles t0, t0 + waves, .. of a pass, nt of them, 3 entries per lane
+// and tile. Every load is issued whatever nt is, a tile past the wave's last
+// reading its first again (no sweep uses it): loads under a test of nt came out
+// as one branch and one wait per tile, four dependent round trips where this is one.
+__device__ __forceinline__ void load_list_tiles(const uint32_t *__restrict__ cand, uint32_t off, uint32_t t0,
+                                                uint32_t nt, uint32_t waves, uint32_t lane,
+                                                uint32_t (&B)[3 * kPpWords]) {
+#pragma unroll
+    for (int k = 0; k < kPpWords; ++k) {
+        const uint32_t tile = t0 + ((uint32_t)k < nt ? (uint32_t)k * waves : 0u);
+        const uint32_t *e = cand + kCandHeader + off + tile * kCandTile + lane;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) B[3 * k + i] = e[i * 64];
+    }
+}
+
+// One wave's share of a class-sorted chunk in the list form. The pods of a
+// digit (a slot of the sort) are contiguous, [b0, b1) those that do not
+// tolerate and [b1, b2) those that do, and so are the digit's lists, S_d's tiles
+// then U_d's. Wave wv takes tiles wv, wv + waves, .. of the digit, up to
+// kPpWords of them per pass (more than kPpWords * waves tiles take further
+// passes; the waves combine by atomicMax on LDS either way), in ONE load round
+// for both tolerations: the S tiles come first, so the first ns of the wave's
+// nt tiles are S_d's (both counts wave-uniform), the pods that do not tolerate
+// are swept through those and the pods that do through all nt, out of the same
+// registers. A pass that holds U tiles only skips the former; a digit none of
+// whose pods tolerates stops at S_d's tiles. A wave with no tile of a digit
+// skips it.
+__device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, const ClassLanes &C,
+                                            const uint2 *pinfo, uint32_t wv, uint32_t waves, uint32_t lane,
+                                            u64 *lds) {
+    for (uint32_t s = 0; s < kPpClasses; s += 2) {
+        const uint32_t b0 = lane_value(C.beg, s), b1 = lane_value(C.end, s), b2 = lane_value(C.end, s + 1u);
+        if (b0 >= b2) continue;
+        const DigitLists L = {lane_value(C.L.off, s), lane_value(C.L.ns, s), lane_value(C.L.nt, s)};
+        const uint32_t ntile = list_tiles(L, b1 < b2);  // (no pod tolerates: S_d's tiles)
         for (uint32_t t0 = wv; t0 < ntile; t0 += kPpWords * waves) {
             const uint32_t nt = min((uint32_t)kPpWords, (ntile - t0 + waves - 1u) / waves);  // >= 1
+            const uint32_t ns = t0 < L.ns ? min((uint32_t)kPpWords, (L.ns - t0 + waves - 1u) / waves) : 0u;
             uint32_t B[3 * kPpWords];
-#pragma unroll
-            for (int k = 0; k < kPpWords; ++k) {
-                const uint32_t *e = cand + kCandHeader + off + (t0 + k * waves) * kCandTile + lane;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) B[3 * k + i] = (uint32_t)k < nt ? e[i * 64] : 0u;
-            }
-            switch (nt) {  // wave-uniform
-                case 1: sweep_list_pods<1>(B, pinfo, beg, end, lane, lds); break;
-                case 2: sweep_list_pods<2>(B, pinfo, beg, end, lane, lds); break;
-                case 3: sweep_list_pods<3>(B, pinfo, beg, end, lane, lds); break;
-                default: sweep_list_pods<4>(B, pinfo, beg, end, lane, lds); break;
-            }
+            load_list_tiles(cand, L.off, t0, nt, waves, lane, B);
+            if (ns != 0u && b0 < b1) sweep_list_tiles(ns, B, pinfo, b0, b1, lane, lds);
+            if (b1 < b2) sweep_list_tiles(nt, B, pinfo, b1, b2, lane, lds);
         }
     }
 }
@@ -500,9 +583,9 @@ __device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, c
 // the same 8-pod blocks (the packed last word's sharing counts them). Without
 // runs, and for kModeGen waves, the chunk is one per-pod range.
 // lists: the chunk is swept in the list form (sweep_lists takes every digit
-// class whose list hdr, the buffer's header, shows non-empty): what is left
-// here, for waves of every mode, are the digit classes with no candidate and
-// the other class, per pod. Their ranges start anywhere; the packed last
+// class for which list_tiles gives a tile): what is left here, for waves of
+// every mode, are the classes of class_lanes' planes, the digit classes it gives
+// none and the other class, per pod. Their ranges start anywhere; the packed last
 // word's sharing only needs every wave to cut the same blocks, which they do
 // (the same beg for all).
 // (Padding every run to whole blocks instead of sweeping the rests per pod
@@ -510,15 +593,26 @@ __device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, c
 template <int KW, int NW, int MODE, bool TAIL>
 __device__ __forceinline__ void sweep_range(const Word (&W)[KW], const Word &Wt, uint32_t tpt, uint32_t tshare,
                                             uint32_t tidx, const uint2 *pinfo, const uint32_t *rb, bool runs,
-                                            bool lists, const uint32_t *hdr, uint32_t np, uint32_t lane, u64 *lds) {
+                                            bool lists, const uint32_t *hdr, uint32_t base10, uint32_t np,
+                                            uint32_t lane, u64 *lds) {
     // (not in the 8-word form: with 24 bases more it needs over 128 VGPRs)
     constexpr bool RUN = MODE != kModeGen && NW > 0 && KW == kPpWords;
     const bool cut = lists || (RUN && runs);
-    for (uint32_t c = cut ? 0u : kPpClasses; c <= kPpClasses; ++c) {
-        const uint32_t beg = cut ? (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c]) : 0u;
-        const uint32_t end = cut ? (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c + 1]) : np;
+    // the classes to take here: those the list form leaves (their bounds a class to a
+    // lane), every class, or the chunk as one range
+    u64 todo = cut ? (2ull << kPpClasses) - 1ull : 1ull << kPpClasses;
+    uint32_t cbeg = 0, cend = 0;
+    if (lists) {
+        const ClassLanes C = class_lanes(hdr, rb, base10, lane);
+        cbeg = C.beg, cend = C.end, todo = C.planes;
+    }
+    for (; todo; todo &= todo - 1ull) {
+        const uint32_t c = (uint32_t)__builtin_ctzll(todo);
+        const uint32_t beg = lists ? lane_value(cbeg, c)
+                             : cut ? (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c]) : 0u;
+        const uint32_t end = lists ? lane_value(cend, c)
+                             : cut ? (uint32_t)__builtin_amdgcn_readfirstlane((int)rb[c + 1]) : np;
         if (beg >= end) continue;
-        if (lists && c < kPpClasses && list_tiles(hdr, pinfo[beg].y, nullptr) != 0u) continue;
         uint32_t B[RUN ? NW * 3 : 1] = {};
         bool form = false;
         if constexpr (RUN)
@@ -715,8 +809,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
 #define MS_PP_CASE1(N, M, T)                                                                                     \
     case 6 * N + 2 * M + T:                                                                                      \
         if constexpr (N <= KW && (N > 0 || T))                                                                   \
-            sweep_range<KW, (N <= KW ? N : KW), M, T>(W, Wt, tpt, tshare, wv - wv_t, pinfo, rb, runs, lists, hdr, np, \
-                                                      lane, lds);                                               \
+            sweep_range<KW, (N <= KW ? N : KW), M, T>(W, Wt, tpt, tshare, wv - wv_t, pinfo, rb, runs, lists, hdr,   \
+                                                      node_base % 10u, np, lane, lds);                          \
         break;
 #define MS_PP_CASE(N)        \
     MS_PP_CASE1(N, 0, false) \
@@ -741,7 +835,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
         }
     }
     if constexpr (KW == kPpWords)
-        if (np && lists) sweep_lists(cand, hdr, pinfo, rb, wv, waves, lane, lds);
+        if (np && lists)
+            sweep_lists(cand, class_lanes(hdr, rb, node_base % 10u, lane), pinfo, wv, waves, lane, lds);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
         const u64 v = lds[i];
@@ -832,20 +927,23 @@ __global__ void k_build_planes(NodeTable t, const NodeDelta *__restrict__ deltas
     if (g < t.gcap) build_group(t, g);
 }
 
-// The rows of group g that a pod of list class c (digit + 10 * tolerates) can win: match10's mask.
+// The rows of group g in list c (ms_internal.h kCand*): the present rows of name digit
+// c mod 10, the schedulable ones for c < 10 (S_d), the unschedulable ones above (U_d).
 __device__ __forceinline__ uint32_t cand_mask(const NodeTable &t, uint32_t g, uint32_t c) {
-    const uint32_t st = t.gcap, v = c % 10u;
+    const uint32_t st = t.gcap, v = c % kCandDigits;
     const uint32_t d0 = t.planes[kPlaneD0 * st + g], d1 = t.planes[kPlaneD1 * st + g];
     const uint32_t d2 = t.planes[kPlaneD2 * st + g], d3 = t.planes[kPlaneD3 * st + g];
-    const uint32_t f = t.planes[(c >= 10u ? kPlanePresent : kPlaneSched) * st + g];
+    const uint32_t sched = t.planes[kPlaneSched * st + g];
+    const uint32_t f = c < kCandDigits ? sched : t.planes[kPlanePresent * st + g] & ~sched;
     return f & ((v & 1u) ? d0 : ~d0) & ((v & 2u) ? d1 : ~d1) & ((v & 4u) ? d2 : ~d2) & ((v & 8u) ? d3 : ~d3);
 }
 
 // The candidate lists (ms_internal.h kCand*) from the planes: block c builds
 // list c. Every block first counts all 20 lists (its list starts after the
-// padded lengths of those before it), then writes its entries in row order:
-// 1024 groups at a time, each thread one group, placed by a block-wide prefix
-// sum of the groups' candidate counts.
+// padded lengths of those before it: the lists of the lower digits, and for
+// U_d also S_d), then writes its entries in row order: 1024 groups at a time,
+// each thread one group, placed by a block-wide prefix sum of the groups'
+// candidate counts.
 constexpr uint32_t kCandThreads = 1024;
 
 __global__ __launch_bounds__(kCandThreads) void k_build_cand(NodeTable t, uint32_t *__restrict__ cand) {
@@ -864,13 +962,19 @@ __global__ __launch_bounds__(kCandThreads) void k_build_cand(NodeTable t, uint32
         if (lane == 0u && sum) atomicAdd(&cnt[k], sum);
     }
     __syncthreads();
+    const uint32_t dg = c % kCandDigits;
     uint32_t off = 0;
-    for (uint32_t k = 0; k < c; ++k) off += cdiv(cnt[k], kCandTile) * kCandTile;
+    for (uint32_t k = 0; k < dg; ++k)
+        off += (cdiv(cnt[k], kCandTile) + cdiv(cnt[kCandDigits + k], kCandTile)) * kCandTile;
+    if (c >= kCandDigits) off += cdiv(cnt[dg], kCandTile) * kCandTile;
     const uint32_t len = cnt[c], padded = cdiv(len, kCandTile) * kCandTile;
     if (tid == 0u) {
-        cand[c] = off;
+        if (c < kCandDigits) {
+            cand[dg] = off;
+            cand[kCandDigits + 1u + dg] = padded / kCandTile;
+        }
         cand[kCandClasses + 1u + c] = len;
-        if (c + 1u == kCandClasses) cand[kCandClasses] = off + padded;
+        if (c + 1u == kCandClasses) cand[kCandDigits] = off + padded;
     }
     uint32_t *ent = cand + kCandHeader + off;
     uint32_t done = 0;  // entries written by the groups before g0
