@@ -203,6 +203,27 @@ int ms_destroy(ms_ctx *ctx);
 const char *ms_last_error(const ms_ctx *ctx);
 int ms_get_info(const ms_ctx *ctx, ms_info *out);
 
+/* Every counter the exact sequential engine's in-order validator keeps, summed
+ * since ms_create (diagnostics; ms_info carries three of them). A pod is decided
+ * by its speculative winner, by re-resolving its top-4 and the merge's certified
+ * ranks, or, as a "slow" pod, alone against the current state; a slow pod whose
+ * certified ranks are all bound scans the tile lists, and a tile whose full
+ * list is all bound is swept again. Read after the same stream synchronise as
+ * ms_get_info. Additive to ABI 7 (MS_ABI_VERSION and ms_info unchanged): a
+ * caller detects the feature by the symbol. The struct has no typedef (the
+ * name is the function's): write `struct ms_seq_counters`. */
+struct ms_seq_counters {
+    uint32_t overflow;      /* non-zero: a validator capacity violation (ms_info._pad) */
+    uint32_t resweep_tiles; /* tiles swept again by a list scan (ms_info.seq_resweep_tiles) */
+    uint32_t recomputes;    /* listed entries re-evaluated from a bound node's record  */
+    uint32_t pods;          /* pods validated                                          */
+    uint32_t misses;        /* winners outside the pod's top-4 (records loaded)        */
+    uint32_t slow_pods;     /* pods resolved alone                                     */
+    uint32_t list_scans;    /* slow pods that scanned the tile lists                   */
+    uint32_t _pad;
+};
+int ms_seq_counters(const ms_ctx *ctx, struct ms_seq_counters *out);
+
 /* Host-side phase times of the last ms_schedule_batch / ms_schedule_batch_compact
  * call on ctx (diagnostics: where a slow host call spent its wall time). ns[]
  * is indexed by MS_PH_*; every phase is host wall time inside the call, and

@@ -286,6 +286,26 @@ int ms_get_info(const ms_ctx *c, ms_info *out) {
     return MS_OK;
 }
 
+int ms_seq_counters(const ms_ctx *c, struct ms_seq_counters *out) {
+    if (!c || !out) return MS_E_INVAL;
+    ms_ctx *m = const_cast<ms_ctx *>(c);
+    std::lock_guard<std::mutex> g(m->delta_mu);
+    uint32_t st[7] = {0, 0, 0, 0, 0, 0, 0};
+    // (as ms_get_info: the counters are written on the context stream)
+    if (hipSetDevice(c->cfg.device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+        hipMemcpy(st, c->d_overflow, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(m, MS_E_HIP, "ms_seq_counters: counter read-back");
+    out->overflow = st[0];
+    out->resweep_tiles = st[1];
+    out->recomputes = st[2];
+    out->pods = st[3];
+    out->misses = st[4];
+    out->slow_pods = st[5];
+    out->list_scans = st[6];
+    out->_pad = 0;
+    return MS_OK;
+}
+
 int ms_nodes_upsert(ms_ctx *c, uint32_t n, const uint32_t *ord, const ms_node_rec *recs) {
     if (!c || (n && (!ord || !recs))) return MS_E_INVAL;
     std::lock_guard<std::mutex> g(c->delta_mu);

@@ -245,6 +245,12 @@ class ms_info(ctypes.Structure):
     ]
 
 
+class ms_seq_counters(ctypes.Structure):
+    """struct ms_seq_counters: the sequential validator's counters since ms_create."""
+    _fields_ = [(f, ctypes.c_uint32) for f in ("overflow", "resweep_tiles", "recomputes", "pods", "misses", "slow_pods",
+                                               "list_scans", "_pad")]
+
+
 COMM_ID_BYTES = 128  # MS_COMM_ID_BYTES (an ncclUniqueId)
 
 
@@ -261,6 +267,7 @@ SIGNATURES = {
     "ms_destroy": (ctypes.c_int, [_vp]),
     "ms_last_error": (ctypes.c_char_p, [_vp]),
     "ms_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(ms_info)]),
+    "ms_seq_counters": (ctypes.c_int, [_vp, ctypes.POINTER(ms_seq_counters)]),
     "ms_last_call_profile": (ctypes.c_int, [_vp, ctypes.POINTER(ms_call_profile)]),
     "ms_nodes_upsert": (ctypes.c_int, [_vp, _u32, _vp, _vp]),
     "ms_nodes_delete": (ctypes.c_int, [_vp, _u32, _vp]),
@@ -415,6 +422,12 @@ class Engine:
     def info(self) -> ms_info:
         out = ms_info()
         self._check("ms_get_info", self.lib.ms_get_info(self.h, ctypes.byref(out)))
+        return out
+
+    def seq_counters(self) -> ms_seq_counters:
+        """ms_seq_counters: every counter of the sequential validator (ms_info has three)."""
+        out = ms_seq_counters()
+        self._check("ms_seq_counters", self.lib.ms_seq_counters(self.h, ctypes.byref(out)))
         return out
 
     def last_call_profile(self) -> dict:

@@ -393,18 +393,28 @@ def test_chunked_batches(oracle):
         assert_same(e.schedule(pr, MODE_SEQUENTIAL), o)
 
 
-@pytest.mark.parametrize("max_batch", [8300, 8320, 8384])
+@pytest.mark.parametrize("max_batch", [8300, 8320, 8384, 8256, 8488])
 def test_chunked_warm_runs(oracle, max_batch):
     # every chunk of a call is a sequential run that opens with warm-up batches of
-    # 64 (its first 8,192 pods), so only pods 0..63 of a list set are rewritten
+    # 64 (its first 4,096 pods), so only pods 0..63 of a list set are rewritten
     # until its first full-size batch; cells left over from the previous chunk
     # must never pass for swept ones (the 2-bit list tag repeats every third
-    # step: three chunk sizes, three tag phases), nor across two calls
+    # step), nor across two calls. The tag sequence is restated in tests/_seq_tags.py
+    # (tests/test_seq_tags.py derives every size on the CPU): without the clearing at
+    # the start of a run, 8256 and 8488 leave in slots 64.. of a list set the very tag
+    # the next chunk's first full-size batch waits for, and 8384 the tag of a later
+    # chunk's batches 1 and 65; 8300 and 8320 (sized for the earlier 8,192-pod
+    # warm-up) leave other tags everywhere
+    import _seq_tags
+
     seed = max_batch
     nr = synth.nodes(3000, seed=seed, resources=True)
     pr = synth.pods(3 * max_batch + 77, seed=seed, resources=True)
-    o = oracle.schedule(nr, pr, plugin_set=1, mode=1, seed=seed)
     half = len(pr) // 2
+    calls = [half, len(pr) - half]
+    assert not _seq_tags.collisions(calls, max_batch, clear=True)
+    assert bool(_seq_tags.collisions(calls, max_batch, clear=False)) == (max_batch in (8384, 8256, 8488))
+    o = oracle.schedule(nr, pr, plugin_set=1, mode=1, seed=seed)
     with engine_with(nr, plugin_set=PLUGINS_NU_NRF_NN_LA, seed=seed, max_batch=max_batch) as e:
         a = e.schedule(pr[:half], MODE_SEQUENTIAL)
         b = e.schedule(pr[half:], MODE_SEQUENTIAL)
