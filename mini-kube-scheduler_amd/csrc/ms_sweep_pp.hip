@@ -54,14 +54,22 @@
 // Grid: a workgroup holds ALL of the context's rows (up to 16 waves x 64 lanes
 // x kPpWords groups = 122,880 rows; more rows split over grid.y and combine
 // with atomicMax) and sweeps a chunk of pods through them, 8 pods at a time.
-// The 8 lane maxima are reduced by one transposed butterfly (reduce8), the
-// waves combine in LDS (ds_max_u64 of level<<32 | hash), and after one barrier
-// the workgroup unhashes each pod's winner (tb_unhash) and writes either the
-// packed key (ms_sweep_device: one plain store per pod, no zeroing, no
-// atomics) or the decoded ms_result directly (the fused single-shard cycle).
+// From the planes, the 8 lane maxima are reduced by one transposed butterfly
+// (reduce8) and the waves combine in LDS (ds_max_u64 of level<<32 | hash): a
+// wave needs its own maximum there, to redo a pod whose maximum is 0. The list
+// form needs no such thing, so where LDS allows (lane_table_fits) it combines
+// the other way round: every wave puts its lane maxima into the pod's row of a
+// lane table, lane by lane (ds_max_u32, no cross-lane instruction in the
+// sweep), and after the sweep's barrier the workgroup reduces each row once
+// into the pod's slot; where the table does not fit, the list form reduces per
+// wave like the planes. After one more barrier the workgroup unhashes each
+// pod's winner (tb_unhash) and writes either the packed key (ms_sweep_device:
+// one plain store per pod, no zeroing, no atomics) or the decoded ms_result
+// directly (the fused single-shard cycle).
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "ms_device.h"
@@ -472,8 +480,42 @@ __device__ __forceinline__ ClassLanes class_lanes(const uint32_t *hdr, const uin
     return C;
 }
 
+// A pod of class c (pod_class) of a list-form chunk is swept by sweep_lists: the
+// complement of class_lanes' planes for the classes that hold a pod, asked per pod
+// (the lane table's final pass).
+__device__ __forceinline__ bool list_covered(const uint32_t *hdr, uint32_t c, uint32_t base10) {
+    return c < kPpClasses && list_tiles(digit_lists(hdr, ((c >> 1) + base10) % kCandDigits), (c & 1u) != 0u) != 0u;
+}
+
 __device__ __forceinline__ uint32_t lane_value(uint32_t v, uint32_t l) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
+}
+
+// The lane table (LT = 64 words per pod position, a word to a lane; after the sort
+// words in LDS, zeroed by the prologue). In the list form a pod's candidates are spread
+// over all the waves' lanes, and every lane's maximum is a candidate's hash, so
+// the lane maxima need no reduction in the wave: a wave puts them into the
+// pod's row of the table by ds_max_u32, lane by lane, and the workgroup reduces
+// each row once after the sweep (table_rowmax, the kernel's final pass). A wave
+// held 9 to 12 entries per lane at config C and paid the 8-pod butterfly for
+// every 50 to 66 hash instructions per pod; this way it pays one LDS
+// instruction per pod and no cross-lane one. (32 words per pod, reduce8's first
+// stage in front of 4 ds_max_u32 per block, gained half as much at config C:
+// profiles/r15a_lane_table_ab.txt.)
+// row: the block's first row plus the lane (table + (first pod) * LT + lane), so
+// consecutive lanes hit consecutive banks and the pods differ by the
+// instruction's offset field alone. n: the pods present in the block
+// (wave-uniform); the absent ones write nothing.
+__device__ __forceinline__ void lds_max_u32(uint32_t *p, uint32_t v) {
+    __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // (no return value: ds_max_u32)
+}
+
+template <int LT>
+__device__ __forceinline__ void table_put(uint32_t *row, const uint32_t (&r)[8], uint32_t n) {
+    static_assert(LT == 64, "a word to a lane");
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+        if ((uint32_t)t < n) lds_max_u32(row + t * LT, r[t]);
 }
 
 // One wave sweeps the pods [beg, end) of one class through NT tiles of the
@@ -483,9 +525,11 @@ __device__ __forceinline__ uint32_t lane_value(uint32_t v, uint32_t l) {
 // that is the hash of a real candidate then, and no redo is needed.
 // The range may start anywhere and its last block hold fewer than 8 pods,
 // whose absent pods are not hashed (wave-uniform tests).
-template <int NT>
+// LT != 0: the lane maxima go to the lane table (tabl: the table plus the lane);
+// else they are reduced here (reduce8) and combined in the pods' slots.
+template <int NT, int LT>
 __device__ __forceinline__ void sweep_list_pods(const uint32_t (&B)[3 * kPpWords], const uint2 *pinfo, uint32_t beg,
-                                                uint32_t end, uint32_t lane, u64 *lds) {
+                                                uint32_t end, uint32_t lane, u64 *lds, uint32_t *tabl) {
     for (uint32_t pb = beg; pb < end; pb += 64) {
         const uint32_t nblk = min(64u, end - pb);
         const uint32_t a_l = lane < nblk ? pinfo[pb + lane].x : 0u;
@@ -500,6 +544,7 @@ __device__ __forceinline__ void sweep_list_pods(const uint32_t (&B)[3 * kPpWords
                     for (int i = 0; i < 3 * NT; ++i) h = max(h, mix32(B[i] + A));
                     r[t] = h;
                 }
+                if constexpr (LT != 0) table_put<LT>(tabl + (pb + j) * LT, r, 8u);
             } else {
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
@@ -510,23 +555,41 @@ __device__ __forceinline__ void sweep_list_pods(const uint32_t (&B)[3 * kPpWords
                         for (int i = 0; i < 3 * NT; ++i) r[t] = max(r[t], mix32(B[i] + A));
                     }
                 }
+                if constexpr (LT != 0) table_put<LT>(tabl + (pb + j) * LT, r, nblk - j);
             }
-            const uint32_t u = reduce8(r, lane);
-            const uint32_t pi = j + rev3(lane >> 3);  // lanes 8k: pod pi of the block
-            if ((lane & 7u) == 0u && pi < nblk) atomicMax(&lds[pb + pi], (11ull << 32) | u);
+            if constexpr (LT == 0) {
+                const uint32_t u = reduce8(r, lane);
+                const uint32_t pi = j + rev3(lane >> 3);  // lanes 8k: pod pi of the block
+                if ((lane & 7u) == 0u && pi < nblk) atomicMax(&lds[pb + pi], (11ull << 32) | u);
+            }
         }
     }
 }
 
 // (sweep_list_pods over the first n of the lane's tiles)
+template <int LT>
 __device__ __forceinline__ void sweep_list_tiles(uint32_t n, const uint32_t (&B)[3 * kPpWords], const uint2 *pinfo,
-                                                 uint32_t beg, uint32_t end, uint32_t lane, u64 *lds) {
+                                                 uint32_t beg, uint32_t end, uint32_t lane, u64 *lds, uint32_t *tabl) {
     switch (n) {  // wave-uniform
-        case 1: sweep_list_pods<1>(B, pinfo, beg, end, lane, lds); break;
-        case 2: sweep_list_pods<2>(B, pinfo, beg, end, lane, lds); break;
-        case 3: sweep_list_pods<3>(B, pinfo, beg, end, lane, lds); break;
-        default: sweep_list_pods<4>(B, pinfo, beg, end, lane, lds); break;
+        case 1: sweep_list_pods<1, LT>(B, pinfo, beg, end, lane, lds, tabl); break;
+        case 2: sweep_list_pods<2, LT>(B, pinfo, beg, end, lane, lds, tabl); break;
+        case 3: sweep_list_pods<3, LT>(B, pinfo, beg, end, lane, lds, tabl); break;
+        default: sweep_list_pods<4, LT>(B, pinfo, beg, end, lane, lds, tabl); break;
     }
+}
+
+// The maximum of row i of the lane table, in the last of the LT / 4 = 16
+// consecutive lanes (a DPP row) that read it, 4 words each (one ds_read_b128; the
+// other lanes hold partial maxima). Every lane of the wave takes part.
+template <int LT>
+__device__ __forceinline__ uint32_t table_rowmax(const uint32_t *tab, uint32_t i, uint32_t sub) {
+    const uint4 q = *reinterpret_cast<const uint4 *>(tab + i * LT + sub * 4u);
+    uint32_t m = max(max(q.x, q.y), max(q.z, q.w));
+    m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x111, 0xF, 0xF, false));  // row_shr:1
+    m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x112, 0xF, 0xF, false));  // row_shr:2
+    m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x114, 0xF, 0xF, false));  // row_shr:4
+    m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x118, 0xF, 0xF, false));  // row_shr:8
+    return m;
 }
 
 // The wave's tiles t0, t0 + waves, .. of a pass, nt of them, 3 entries per lane
@@ -557,9 +620,10 @@ __device__ __forceinline__ void load_list_tiles(const uint32_t *__restrict__ can
 // registers. A pass that holds U tiles only skips the former; a digit none of
 // whose pods tolerates stops at S_d's tiles. A wave with no tile of a digit
 // skips it.
+template <int LT>
 __device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, const ClassLanes &C,
                                             const uint2 *pinfo, uint32_t wv, uint32_t waves, uint32_t lane,
-                                            u64 *lds) {
+                                            u64 *lds, uint32_t *tabl) {
     for (uint32_t s = 0; s < kPpClasses; s += 2) {
         const uint32_t b0 = lane_value(C.beg, s), b1 = lane_value(C.end, s), b2 = lane_value(C.end, s + 1u);
         if (b0 >= b2) continue;
@@ -570,8 +634,8 @@ __device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, c
             const uint32_t ns = t0 < L.ns ? min((uint32_t)kPpWords, (L.ns - t0 + waves - 1u) / waves) : 0u;
             uint32_t B[3 * kPpWords];
             load_list_tiles(cand, L.off, t0, nt, waves, lane, B);
-            if (ns != 0u && b0 < b1) sweep_list_tiles(ns, B, pinfo, b0, b1, lane, lds);
-            if (b1 < b2) sweep_list_tiles(nt, B, pinfo, b1, b2, lane, lds);
+            if (ns != 0u && b0 < b1) sweep_list_tiles<LT>(ns, B, pinfo, b0, b1, lane, lds, tabl);
+            if (b1 < b2) sweep_list_tiles<LT>(nt, B, pinfo, b1, b2, lane, lds, tabl);
         }
     }
 }
@@ -672,7 +736,9 @@ struct PpJob2 {
 
 // TP: the packed-last-word path is compiled in (launch_sweep_pp picks it only
 // for shapes tail_pods packs; the others run the plain form).
-template <int KW, bool TP>
+// LT: words per pod of the lane table (0: none; launch_sweep_pp picks it for
+// list-form chunks whose table fits, lane_table_fits).
+template <int KW, bool TP, int LT>
 __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     const uint32_t *__restrict__ planes, uint32_t gstride, uint32_t n_groups, uint32_t node_base,
     const ms_pod_rec *__restrict__ pods1, uint32_t n_pods1, uint32_t chunk, uint32_t seed32, u64 *__restrict__ keys1,
@@ -680,9 +746,10 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     uint32_t pstride, ms_result_compact *__restrict__ resc, PpJob2 j2, int fix_ok, uint32_t xtra,
     const uint32_t *__restrict__ cand) {
     // LDS: one combine slot per pod of the chunk, then the chunk's pod entries,
-    // then the kPpSortWords words of the class sort
+    // then the kPpSortWords words of the class sort, then (LT != 0) the lane
+    // table: LT words per pod position
     // (xtra: workgroups 0 .. xtra-1 take chunk + 8 pods, the balanced split)
-    extern __shared__ u64 lds[];
+    extern __shared__ __attribute__((aligned(16))) u64 lds[];
     uint2 *pinfo = reinterpret_cast<uint2 *>(lds + chunk + (xtra ? 8u : 0u));
     const uint32_t lane = lane_id();
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -701,6 +768,12 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     // the list form: this workgroup holds every row (else the workgroups of a chunk
     // would each sweep the whole list)
     const bool lists = runs && cand != nullptr && gridDim.y == 1u;
+    uint32_t *ltab = hdr + 24;
+    if constexpr (LT != 0) {
+        // (16-byte stores; the sort's barriers come before the sweep)
+        uint4 *z = reinterpret_cast<uint4 *>(ltab);
+        for (uint32_t i = threadIdx.x; i < np * (LT / 4); i += blockDim.x) z[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
     if (!runs) {
         for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
             lds[i] = 0;
@@ -836,8 +909,28 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     }
     if constexpr (KW == kPpWords)
         if (np && lists)
-            sweep_lists(cand, class_lanes(hdr, rb, node_base % 10u, lane), pinfo, wv, waves, lane, lds);
+            sweep_lists<LT>(cand, class_lanes(hdr, rb, node_base % 10u, lane), pinfo, wv, waves, lane, lds,
+                            ltab + lane);
     __syncthreads();
+    if constexpr (LT != 0) {
+        // The lane table's final pass, once per pod: LT / 4 lanes to a row. A list-form
+        // maximum is level 11 whatever its value (0 is a real candidate's hash), so what
+        // says that a row holds one is the pod's class (list_covered). The pod's slot may
+        // hold the planes path's value; an uncovered pod keeps it alone.
+        if (np && lists) {  // (workgroup-uniform)
+            constexpr uint32_t G = LT / 4;
+            const uint32_t sub = threadIdx.x % G;
+            for (uint32_t i0 = 0; i0 < np; i0 += blockDim.x / G) {
+                const uint32_t i = i0 + threadIdx.x / G;
+                const uint32_t m = table_rowmax<LT>(ltab, min(i, np - 1u), sub);
+                if (sub == G - 1u && i < np) {
+                    if (list_covered(hdr, pod_class(pinfo[i].y), node_base % 10u))
+                        lds[i] = umax64(lds[i], (11ull << 32) | m);
+                }
+            }
+        }
+        __syncthreads();
+    }
     for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
         const u64 v = lds[i];
         const uint2 pe = pinfo[i];
@@ -1030,7 +1123,46 @@ hipError_t launch_build_planes(const NodeTable &t, uint32_t *cand, const NodeDel
 // pods, else 32) in multiples of 8, at most kPpMaxChunk (LDS).
 constexpr uint32_t kPpMaxChunk = 2048;
 
+// LDS of one workgroup whose largest chunk holds cap pods: slots, entries and sort
+// words, and with lt != 0 a lane table of lt words per pod (k_sweep_nunn_pp).
+constexpr uint32_t kPpLdsPerCu = 160u * 1024u;
+constexpr int kPpLaneWords = 64;
+
+__host__ inline uint32_t pp_lds_bytes(uint32_t cap, uint32_t lt) {
+    return cap * (uint32_t)(sizeof(u64) + sizeof(uint2)) + kPpSortWords * (uint32_t)sizeof(uint32_t) +
+           cap * lt * (uint32_t)sizeof(uint32_t);
+}
+
+// Where the list sweep combines through the lane table: the chunk is sorted (so
+// that, with lists and one workgroup per chunk, it is swept in the list form), and
+// with the table per_cu workgroups, the number the geometry sized the chunk for,
+// still fit a CU's LDS together (each rounded up to 2 KiB, no finer than the
+// allocation granule). Else the sweep reduces per wave as before: a table that
+// cost residency would cost more than the reductions it saves.
+__host__ inline bool lane_table_fits(uint32_t chunk, uint32_t xtra, uint32_t W, uint32_t per_cu) {
+    if (chunk < kPpSortMin || W > (uint32_t)kPpMaxWaves) return false;
+    const uint32_t wg = (pp_lds_bytes(chunk + (xtra ? 8u : 0u), (uint32_t)kPpLaneWords) + 2047u) / 2048u * 2048u;
+    return wg * per_cu <= kPpLdsPerCu;
+}
+
 namespace {
+// hipFuncAttributeMaxDynamicSharedMemorySize of one instantiation (the flags are
+// per kernel, not per kernel type), a CU's whole LDS, set once per device (two
+// threads setting it at once set the same value).
+template <auto kernel>
+hipError_t allow_lds() {
+    static std::atomic<bool> set[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !set[dev].load(std::memory_order_acquire)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kPpLdsPerCu);
+        if (e == hipSuccess && dev >= 0 && dev < 64) set[dev].store(true, std::memory_order_release);
+    }
+    return e;
+}
+
 hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
                          uint32_t seed32, unsigned long long *keys, ms_result *results, uint32_t present, int num_cus,
                          hipStream_t s, int commit, hipEvent_t done, uint32_t pstride, ms_result_compact *resc,
@@ -1077,14 +1209,18 @@ hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_ro
         const uint32_t resident = std::max(1u, per_cu * cus / gy);
         return cdiv(cdiv(n_all, resident), 8) * 8;
     };
-    uint32_t chunk = chunk_for(std::max(1u, 32u / W));  // one round at 32 waves per CU
+    uint32_t per_cu = std::max(1u, 32u / W);  // workgroups per CU the chunk is sized for
+    uint32_t chunk = chunk_for(per_cu);       // one round at 32 waves per CU
     // Half as many workgroups (16 waves per CU, 4 per SIMD still saturate VALU
     // issue) while chunks stay modest: each workgroup's fixed costs (plane
     // loads, pod prologue, two barriers, epilogue) are paid half as often.
     // Config C 334 -> 324 us and 350 -> 341 us on two boxes; at 1M pods (chunks
     // near 2k) it was 1.3% slower, at 12.5k rows x 800k pods (784) 1.6% faster
     // (profiles/r02zb_ab_chunk_half.jsonl).
-    if (32u / W > 1u && chunk_for(std::max(1u, 16u / W)) <= 1024u) chunk = chunk_for(std::max(1u, 16u / W));
+    if (32u / W > 1u && chunk_for(std::max(1u, 16u / W)) <= 1024u) {
+        per_cu = std::max(1u, 16u / W);
+        chunk = chunk_for(per_cu);
+    }
     // (Chunks of <= 56 pods for <= 8-wave workgroups sped the shard sweep alone up,
     // 12.5k rows 44.3 -> 43.7 us, 25k 73.3 -> 71.0, 50k 133.0 -> 127.0, but slowed the
     // pipelined sharded step, whose collective and decode kernels then interleave with
@@ -1109,6 +1245,7 @@ hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_ro
                 chunk = cb;
                 xtra = nx;
                 nblk1 = slots;
+                per_cu = 16u / W;
             }
         }
     }
@@ -1123,7 +1260,7 @@ hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_ro
         if (!keys || resc) return hipErrorInvalidValue;
         hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * n_pods, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_sweep_nunn_pp<kPpWords, false>), grid, dim3(64 * W),
+        hipLaunchKernelGGL((k_sweep_nunn_pp<kPpWords, false, 0>), grid, dim3(64 * W),
                            chunk * (sizeof(u64) + sizeof(uint2)) + kPpSortWords * sizeof(uint32_t), s, t.planes,
                            t.gcap, n_groups, t.base, pods, n_pods, chunk, seed32, keys, 1, (ms_result *)nullptr, present,
                            t, 0, (uint32_t)sizeof(ms_pod_rec), (ms_result_compact *)nullptr, PpJob2{}, fix_ok, 0u,
@@ -1136,21 +1273,30 @@ hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_ro
     }
     // done: recorded by the dispatch itself (hipExtLaunchKernel's stop event: no
     // separate event packet between this sweep and the next launch on s)
-    const uint32_t lds = (chunk + (xtra ? 8u : 0u)) * (sizeof(u64) + sizeof(uint2)) + kPpSortWords * sizeof(uint32_t);
+    // the list form (as the kernel decides it) through the lane table where that fits
+    const bool table = KW == (uint32_t)kPpWords && cand != nullptr && lane_table_fits(chunk, xtra, W, per_cu);
+    const uint32_t lds = pp_lds_bytes(chunk + (xtra ? 8u : 0u), table ? (uint32_t)kPpLaneWords : 0u);
     unsigned long long *kk = (results || resc) ? nullptr : keys;
     const int cm = (results || resc) ? commit : 0;
     // (gy == 1: the workgroup holds every group; the 8-word form stays unpacked: its
     // packed instantiation needs 117 VGPRs, half the waves per SIMD it sizes for)
     const bool tp = KW == (uint32_t)kPpWords && tail_pods(n_groups, W) != 0u;
-#define MS_PP_LAUNCH(KWV, TPV)                                                                                     \
-    hipExtLaunchKernelGGL((k_sweep_nunn_pp<KWV, TPV>), grid, dim3(64 * W), lds, s, nullptr, done, 0, t.planes, t.gcap, \
-                          n_groups, t.base, pods, n_pods, chunk, seed32, kk, 0, results, present, t, cm, pstride, resc, j2, \
-                          fix_ok, xtra, cand)
+#define MS_PP_LAUNCH(KWV, TPV, LTV)                                                                                 \
+    hipExtLaunchKernelGGL((k_sweep_nunn_pp<KWV, TPV, LTV>), grid, dim3(64 * W), lds, s, nullptr, done, 0, t.planes,   \
+                          t.gcap, n_groups, t.base, pods, n_pods, chunk, seed32, kk, 0, results, present, t, cm, pstride, \
+                          resc, j2, fix_ok, xtra, cand)
     if (KW == (uint32_t)kPpWordsSmall) {
-        MS_PP_LAUNCH(kPpWordsSmall, false);
+        MS_PP_LAUNCH(kPpWordsSmall, false, 0);
+    } else if (table) {
+        // (a table may pass the 64 KiB a kernel gets of dynamic LDS unasked)
+        const hipError_t e = tp ? allow_lds<k_sweep_nunn_pp<kPpWords, true, kPpLaneWords>>()
+                                : allow_lds<k_sweep_nunn_pp<kPpWords, false, kPpLaneWords>>();
+        if (e != hipSuccess) return e;
+        if (tp) MS_PP_LAUNCH(kPpWords, true, kPpLaneWords);
+        else MS_PP_LAUNCH(kPpWords, false, kPpLaneWords);
     } else {
-        if (tp) MS_PP_LAUNCH(kPpWords, true);
-        else MS_PP_LAUNCH(kPpWords, false);
+        if (tp) MS_PP_LAUNCH(kPpWords, true, 0);
+        else MS_PP_LAUNCH(kPpWords, false, 0);
     }
 #undef MS_PP_LAUNCH
     return hipGetLastError();
