@@ -531,6 +531,21 @@ int ms_schedule_sequential_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec
  *   shard's sweep, ONE grouped reduce-scatter (uint64 MAX of the packed keys,
  *   the filter bytes / uint32 NodeAffinity anchors, the "a node is listed"
  *   flag), the decode of this rank's pod slice, an all-gather of the results;
+ *   MS_PLUGINS_NU_NN_NAM (both modes; the set is stateless): class records
+ *   all-gathered, keys and filter bytes reduce-scattered. The first pass
+ *   composes this shard's rescale record (MS_NAM_SEG_BYTES) per CLASS of the
+ *   batch, (term set id, toleration): min(n_pods, 2 (n_sets + 1)) records per
+ *   rank, not one per pod; after the all-gather the second pass computes this
+ *   shard's keys under the later shards' rescales and its own rows' filter
+ *   bytes (byte 0 NodeUnschedulable, byte 2 NodeAffinity; uint8 MAX = OR).
+ *   CONTRACT: every rank registers the same term-set and required-set tables
+ *   (ms_nam_term_sets(_ext), ms_nam_required_sets) before a collective call:
+ *   the number of registered ids fixes the record count, which sizes the
+ *   all-gather, and the ids name the classes. A caller obligation, like "every
+ *   rank submits the same batches". The tables may be replaced between calls
+ *   (the registration synchronises the device, so batches in flight finish on
+ *   the old ones), on every rank before the next collective call.
+ *   ms_schedule_batch_compact stays refused for this set on such a context;
  *   resource-aware sequential: per batch of pods, every shard's speculative
  *   top-4 with records, one grouped all-gather, the replicated in-order
  *   validation (ms_seq_* above); the queue cursor stays on the device, so
@@ -543,12 +558,20 @@ typedef struct ms_comm_id {
 } ms_comm_id;
 int ms_comm_id_create(ms_comm_id *out);
 int ms_comm_init(ms_ctx *ctx, const ms_comm_id *id, int32_t rank, int32_t world);
+/* 1 when the collective calls of a joined context serve plugin_set (0..4 in
+ * this library: MS_PLUGINS_NU_NN_NAM since the in-library class-record cycle),
+ * 0 otherwise. Needs no context. Additive to ABI 7 (MS_ABI_VERSION unchanged):
+ * a caller detects the function by its symbol; a library without it serves
+ * sets 0..3 on a joined context and returns MS_E_INVAL for set 4. */
+int ms_comm_plugin_set_supported(int32_t plugin_set);
 
 /* Pipelined node-sharded batched cycle on device-resident pods (the bench's
  * and a service loop's step). ms_sharded_submit sweeps this shard on `stream`
  * (after the work already there: the pods), runs the batch's collective on the
  * context's collective stream (the grouped reduce-scatter; for
- * MS_PLUGINS_NU_TT_NN an all-to-all of the per-pod summaries) and, once more
+ * MS_PLUGINS_NU_TT_NN an all-to-all of the per-pod summaries; for
+ * MS_PLUGINS_NU_NN_NAM class records all-gathered, keys and filter bytes
+ * reduce-scattered, under the contract stated at ms_comm_init) and, once more
  * than the pipeline depth (4) batches are in flight, decodes the oldest ones
  * on the context's decode stream: batch k's collective overlaps the sweeps of
  * the following batches. ms_sharded_drain decodes every remaining batch and

@@ -477,7 +477,10 @@ __device__ __forceinline__ uint32_t word_digit(uint32_t w) {
 // digit class, the class's maximum of F + 1 (fmax[c * 11 + d], atomicMax; 0:
 // no feasible row). local: k_nam_seg's records [seg][stride]; after / m_in
 // (node shards): the later shards' composed table and "an earlier shard has a
-// non-zero node", read at the class's representative pod, or null.
+// non-zero node", or null: read at the class's representative pod (the per-pod
+// records ms_nam_keys_device composes), or with kByClass at the class index
+// itself (the in-library cycle composes per class: launch_nam_class_keys).
+template <bool kByClass>
 __global__ __launch_bounds__(64) void k_nam_fscore(NodeTable t, uint32_t n_rows, uint32_t seg_rows,
                                                    const NamTab *__restrict__ sets, uint32_t n_sets,
                                                    const uint32_t *__restrict__ ctl,
@@ -502,7 +505,7 @@ __global__ __launch_bounds__(64) void k_nam_fscore(NodeTable t, uint32_t n_rows,
     // T_{>segment}: the later segments' tables, then the later shards'
     uint8_t *mine = tabs + lane * kNamStride;
     table_identity(mine);
-    const uint32_t rp = live ? rep[c] : 0u;
+    const uint32_t rp = live ? (kByClass ? c : rep[c]) : 0u;
     uint32_t before = (live && m_in) ? m_in[rp] : 0u;
     if (live) {
         for (uint32_t s = 0; s < seg; ++s) before |= local[(size_t)s * stride + c].any;
@@ -793,24 +796,31 @@ hipError_t launch_nam_flags(const void *in, uint32_t stride, uint32_t n, uint32_
     return hipGetLastError();
 }
 
-hipError_t launch_nam_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
-                           const void *sets, uint32_t n_sets, uint32_t seed32, uint32_t w_nn, uint32_t w_na,
-                           const void *after, const uint8_t *m_in, uint32_t listed, const NamLayout &L,
-                           void *scratch, unsigned long long *keys, uint32_t *flags, hipStream_t s) {
-    if (n_pods == 0) return hipSuccess;
-    if (!nam_launch_ok(L, n_pods, n_sets)) return hipErrorInvalidValue;
-    const NamScratch x = nam_carve(scratch, L, n_pods, n_sets);
-    hipError_t e = nam_classes_and_segs(t, n_rows, pods, n_pods, sets, n_sets, L, x, s);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(x.fmax, 0, (size_t)L.cls_max * kNamDigits * 4, s);
+namespace {
+// The passes behind the class pass: every class's row scores F under the later
+// segments' and (after / m_in) the later shards' rescales, then per pod the best
+// key. by_class: after / m_in hold one entry per class, not per pod.
+hipError_t nam_scores_and_pick(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+                               const void *sets, uint32_t n_sets, uint32_t seed32, uint32_t w_nn, uint32_t w_na,
+                               const void *after, const uint8_t *m_in, bool by_class, uint32_t listed,
+                               const NamLayout &L, const NamScratch &x, unsigned long long *keys, uint32_t *flags,
+                               hipStream_t s) {
+    hipError_t e = hipMemsetAsync(x.fmax, 0, (size_t)L.cls_max * kNamDigits * 4, s);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(x.F, 0xFF, (size_t)L.cls_max * L.fpitch, s);  // (rows past n_rows: never tied)
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_nam_dmask, dim3(cdiv(L.fpitch, 256u)), dim3(256), 0, s, t, n_rows, L.fpitch, x.dmask);
-    hipLaunchKernelGGL(k_nam_fscore, dim3(cdiv(L.cls_max, 64u), L.segs), dim3(64), 0, s, t, n_rows, L.seg_rows,
-                       static_cast<const NamTab *>(sets), n_sets, (const uint32_t *)x.ctl, (const uint32_t *)x.cls_key,
-                       (const uint32_t *)x.rep, (const NamSeg *)x.local, L.cls_max, L.segs,
-                       static_cast<const NamSeg *>(after), m_in, x.F, L.fpitch, x.fmax);
+    const dim3 fg(cdiv(L.cls_max, 64u), L.segs);
+    if (by_class)
+        hipLaunchKernelGGL(k_nam_fscore<true>, fg, dim3(64), 0, s, t, n_rows, L.seg_rows,
+                           static_cast<const NamTab *>(sets), n_sets, (const uint32_t *)x.ctl,
+                           (const uint32_t *)x.cls_key, (const uint32_t *)x.rep, (const NamSeg *)x.local, L.cls_max,
+                           L.segs, static_cast<const NamSeg *>(after), m_in, x.F, L.fpitch, x.fmax);
+    else
+        hipLaunchKernelGGL(k_nam_fscore<false>, fg, dim3(64), 0, s, t, n_rows, L.seg_rows,
+                           static_cast<const NamTab *>(sets), n_sets, (const uint32_t *)x.ctl,
+                           (const uint32_t *)x.cls_key, (const uint32_t *)x.rep, (const NamSeg *)x.local, L.cls_max,
+                           L.segs, static_cast<const NamSeg *>(after), m_in, x.F, L.fpitch, x.fmax);
     // row parts: enough waves to keep the row stream busy (~16 per SIMD at 50k pods),
     // each part a multiple of kNamPickRows rows
     const uint32_t pod_blocks = cdiv(n_pods, 64u);
@@ -826,6 +836,61 @@ hipError_t launch_nam_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec
                        (const uint32_t *)x.fmax, (const uint8_t *)x.dmask, n_rows, rows_per_part, t.base, seed32, w_nn,
                        w_na, reinterpret_cast<u64 *>(keys), (const NamSeg *)x.local, L.cls_max, L.segs, flags);
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_nam_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+                           const void *sets, uint32_t n_sets, uint32_t seed32, uint32_t w_nn, uint32_t w_na,
+                           const void *after, const uint8_t *m_in, uint32_t listed, const NamLayout &L,
+                           void *scratch, unsigned long long *keys, uint32_t *flags, hipStream_t s) {
+    if (n_pods == 0) return hipSuccess;
+    if (!nam_launch_ok(L, n_pods, n_sets)) return hipErrorInvalidValue;
+    const NamScratch x = nam_carve(scratch, L, n_pods, n_sets);
+    const hipError_t e = nam_classes_and_segs(t, n_rows, pods, n_pods, sets, n_sets, L, x, s);
+    if (e != hipSuccess) return e;
+    return nam_scores_and_pick(t, n_rows, pods, n_pods, sets, n_sets, seed32, w_nn, w_na, after, m_in, false, listed, L,
+                               x, keys, flags, s);
+}
+
+// ---- the in-library node-sharded cycle (ms_comm.cpp): class records -----------
+// A pod's record depends only on its class, and k_nam_index numbers the classes
+// densely in key order from the pods and n_sets alone, so class c is the same
+// class on every shard of a batch: the shards exchange L.cls_max class records
+// instead of n_pods pod records, and the second pass composes per class.
+
+hipError_t launch_nam_class_segment(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+                                    const void *sets, uint32_t n_sets, const NamLayout &L, void *scratch,
+                                    void *cls_out, hipStream_t s) {
+    if (n_pods == 0) return hipSuccess;
+    if (!nam_launch_ok(L, n_pods, n_sets)) return hipErrorInvalidValue;
+    const NamScratch x = nam_carve(scratch, L, n_pods, n_sets);
+    hipError_t e = nam_classes_and_segs(t, n_rows, pods, n_pods, sets, n_sets, L, x, s);
+    if (e != hipSuccess) return e;
+    // (the records past the class count are sent too: identity, no bits)
+    e = launch_nam_identity(cls_out, L.cls_max, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_nam_compose, dim3(cdiv(L.cls_max, kNamComposeThreads)), dim3(kNamComposeThreads), 0, s,
+                       (const NamSeg *)x.local, L.cls_max, L.segs, L.cls_max, -1, static_cast<NamSeg *>(cls_out),
+                       (uint8_t *)nullptr, (const uint32_t *)x.ctl);
+    return hipGetLastError();
+}
+
+hipError_t launch_nam_class_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+                                 const void *sets, uint32_t n_sets, uint32_t seed32, uint32_t w_nn, uint32_t w_na,
+                                 const void *cls_all, uint32_t n_shards, uint32_t shard_index, uint32_t listed,
+                                 const NamLayout &L, void *scratch, void *after, uint8_t *m_in,
+                                 unsigned long long *keys, uint32_t *flags, hipStream_t s) {
+    if (n_pods == 0) return hipSuccess;
+    if (!nam_launch_ok(L, n_pods, n_sets) || shard_index >= n_shards) return hipErrorInvalidValue;
+    // (the scratch holds the first pass's class pass: running it again here cost 0.30 ms of a
+    // 1.01 ms step at 12.5k rows x 100k pods, profiles/r15a_nam_inlibrary.txt)
+    const NamScratch x = nam_carve(scratch, L, n_pods, n_sets);
+    // per class: the later shards' tables composed, and whether an earlier shard has a non-zero node
+    hipLaunchKernelGGL(k_nam_compose, dim3(cdiv(L.cls_max, kNamComposeThreads)), dim3(kNamComposeThreads), 0, s,
+                       static_cast<const NamSeg *>(cls_all), L.cls_max, n_shards, L.cls_max, (int32_t)shard_index,
+                       static_cast<NamSeg *>(after), m_in, (const uint32_t *)x.ctl);
+    return nam_scores_and_pick(t, n_rows, pods, n_pods, sets, n_sets, seed32, w_nn, w_na, after, m_in, true, listed, L, x,
+                               keys, flags, s);
 }
 
 }  // namespace msgpu

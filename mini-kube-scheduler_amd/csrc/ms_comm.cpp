@@ -18,6 +18,10 @@
 //   flags  NodeResourcesFit set: uint8 MAX of the filter bytes (byte-wise OR =
 //          FitError's UnschedulablePlugins over the cluster, :130-137);
 //          NodeAffinity set: uint32 MAX of the normalise anchors;
+//          multi-term NodeAffinity set: uint8 MAX of its filter bytes, after a
+//          first pass whose class records (one rescale record per (term set,
+//          toleration) class of the batch) were all-gathered and a second pass
+//          that computed the keys under them (nam_sharded_sweep);
 // -> the decode of the slice on the caller's stream. Pipelined: the decodes of
 // batch k are enqueued once `depth` later batches were submitted, so batch k's
 // collective overlaps their sweeps. The sweeps run on the caller's stream, the
@@ -83,7 +87,12 @@ struct ShardSlot {
     // order), every shard's after the all-gather (G x G x cap, shard-major,
     // stride = the batch), and the slice's plans for the final pass
     DevBuf<void> cen_mine, cen_all, plans;
+    // MS_PLUGINS_NU_NN_NAM: this shard's class records (cls_cap records) and every
+    // shard's after the all-gather (G x cls_cap, shard-major, stride = the batch's
+    // class cap). They grow with the classes of a batch, not with the slice.
+    DevBuf<void> cls_mine, cls_all;
     uint32_t cap = 0;       // pods per slice the buffers hold
+    uint32_t cls_cap = 0;   // class records the NAM buffers hold
 };
 
 // A batch from its submission to its decode (its slot's buffers may be swept
@@ -173,25 +182,31 @@ int drain_locked(ms_ctx *c, size_t k);
 // slot's previous batch has been drained). No synchronise of its own: the
 // runtime's free of the old blocks waits for that batch's decode, so the slot
 // starts over as unused.
-int slot_ensure(ms_ctx *c, uint32_t si, uint32_t per) {
+// cls (MS_PLUGINS_NU_NN_NAM, else 0): the class records of the batch, rounded up
+// to 64; either growth replaces all of the slot's buffers.
+int slot_ensure(ms_ctx *c, uint32_t si, uint32_t per, uint32_t cls) {
     ShardSlot &sl = c->comm->slot[si];
-    if (per <= sl.cap) return MS_OK;
+    if (per <= sl.cap && cls <= sl.cls_cap) return MS_OK;
     const size_t G = (size_t)c->comm->world;
-    const uint32_t cap = std::max<uint32_t>(1024u, cdiv(per, 1024u) * 1024u);
+    const uint32_t cap = std::max(sl.cap, std::max<uint32_t>(1024u, cdiv(per, 1024u) * 1024u));
+    const uint32_t cls_cap = std::max(sl.cls_cap, cdiv(cls, 64u) * 64u);
     // (a submission held back for a partner makes the slot come round one
     // step early, its batch not decoded yet: that decode reads these buffers)
     if (const size_t k = c->comm->order.pending_through(si)) {
         const int rc = drain_locked(c, k);
         if (rc) return rc;
     }
-    sl.cap = 0;
+    sl.cap = sl.cls_cap = 0;
     MS_ORD(c, c->comm->order.regrown(si));
     if (!sl.keys.alloc(G * cap) || !sl.keys_mine.alloc(cap) || !sl.flags.alloc(G * cap) || !sl.flags_mine.alloc(cap) ||
         (c->cfg.plugin_set == MS_PLUGINS_NU_TT_NN &&
          (!sl.cen_mine.alloc(G * cap * MS_TT_CENSUS_BYTES) || !sl.cen_all.alloc(G * G * cap * MS_TT_CENSUS_BYTES) ||
-          !sl.plans.alloc((size_t)cap * MS_TT_CENSUS_BYTES))))
+          !sl.plans.alloc((size_t)cap * MS_TT_CENSUS_BYTES))) ||
+        (cls_cap && (!sl.cls_mine.alloc((size_t)cls_cap * MS_NAM_SEG_BYTES) ||
+                     !sl.cls_all.alloc(G * cls_cap * MS_NAM_SEG_BYTES))))
         return fail(c, MS_E_OOM, "sharded combine buffers");
     sl.cap = cap;
+    sl.cls_cap = cls_cap;
     return MS_OK;
 }
 
@@ -227,11 +242,13 @@ int drain_locked(ms_ctx *c, size_t k) {
         }
     } else {
         SliceJob jobs[kMaxSliceJobs];
-        const bool nrf = c->cfg.plugin_set == MS_PLUGINS_NU_NRF_NN_LA;
+        // filter bytes: the resource-aware set's (bytes 0, 1) and the multi-term NodeAffinity
+        // set's (bytes 0, 2). No present flag for either: key 1 from any shard says a node is listed
+        const bool filt = c->cfg.plugin_set == MS_PLUGINS_NU_NRF_NN_LA || c->cfg.plugin_set == MS_PLUGINS_NU_NN_NAM;
         for (size_t i = 0; i < k; ++i) {
             const Batch &p = m.pending[i];
             const ShardSlot &sl = m.slot[p.slot];
-            jobs[i] = SliceJob{p.pods + p.first, sl.keys_mine, nrf ? sl.flags_mine : nullptr, nullptr, p.results,
+            jobs[i] = SliceJob{p.pods + p.first, sl.keys_mine, filt ? sl.flags_mine : nullptr, nullptr, p.results,
                                p.count, 0};
         }
         MS_HIP(c, launch_decode_slices(jobs, (uint32_t)k, s));
@@ -285,7 +302,8 @@ int collective_locked(ms_ctx *c, const Batch &b, HostClock::time_point &tp) {
     } else {
         r = CCL(ncclGroupStart)();
         if (r == ncclSuccess) r = CCL(ncclReduceScatter)(sl.keys, sl.keys_mine, per, ncclUint64, ncclMax, m.comm, m.cs);
-        if (r == ncclSuccess && ps == MS_PLUGINS_NU_NRF_NN_LA)  // 0/1 bytes: uint8 MAX = OR
+        // 0/1 bytes: uint8 MAX = OR (resource-aware: bytes 0, 1; multi-term NodeAffinity: bytes 0, 2)
+        if (r == ncclSuccess && (ps == MS_PLUGINS_NU_NRF_NN_LA || ps == MS_PLUGINS_NU_NN_NAM))
             r = CCL(ncclReduceScatter)(sl.flags, sl.flags_mine, (size_t)per * 4, ncclUint8, ncclMax, m.comm, m.cs);
         if (r == ncclSuccess && ps == MS_PLUGINS_NU_NN_NA)  // anchors < 2^21: uint32 MAX
             r = CCL(ncclReduceScatter)(sl.flags, sl.flags_mine, per, ncclUint32, ncclMax, m.comm, m.cs);
@@ -348,6 +366,41 @@ int tt2_sharded_sweep(ms_ctx *c, const Batch &b) {
     return MS_OK;
 }
 
+// MS_PLUGINS_NU_NN_NAM, the same two-pass shape: this shard's class records on X
+// (one 104-byte rescale record per (term set, toleration) class of the batch;
+// class ids are the same on every rank), the all-gather of every shard's on the
+// collective stream, then on X again the keys and this shard's filter words,
+// resuming from the class pass the first pass left in the scratch. The shared
+// scratch (d_nam) passes from sweep stream to sweep stream (nam_take / nam_release).
+// In the ordering class the steps are TaintToleration's: cls_mine is written on
+// X after the collective that read the slot's previous contents (begin);
+// cls_all is written by the all-gather and read only by the keys pass of the
+// same batch, which the slot's next all-gather follows through census_done.
+int nam_sharded_sweep(ms_ctx *c, const Batch &b) {
+    CommState &m = *c->comm;
+    ShardSlot &sl = m.slot[b.slot];
+    const uint32_t si = b.slot, n = b.n, C = nam_shard_classes(c, n);
+    const hipStream_t X = b.X;
+    int rc = nam_shard_begin(c, n, X);
+    if (rc) return rc;
+    rc = [&]() -> int {
+        const int seg = nam_shard_segment(c, n, b.pods, sl.cls_mine, X);
+        if (seg) return seg;
+        MS_ORD(c, m.order.census_done(si, X));
+        const ncclResult_t r = CCL(ncclAllGather)(sl.cls_mine, sl.cls_all, (size_t)C * MS_NAM_SEG_BYTES, ncclUint8,
+                                                  m.comm, m.cs);
+        if (r != ncclSuccess) return fail(c, MS_E_RCCL, std::string("NodeAffinity class record all-gather: ") +
+                                                            CCL(ncclGetErrorString)(r));
+        MS_ORD(c, m.order.gathered(si, X));
+        return nam_shard_keys(c, n, b.pods, sl.cls_all, (uint32_t)m.world, (uint32_t)m.rank, sl.keys, sl.flags, X);
+    }();
+    // (after a failure too: the next cycle on another stream follows what this one enqueued)
+    const int released = nam_release(c, X);
+    if (rc || released) return rc ? rc : released;
+    MS_ORD(c, m.order.swept(si, X, false));  // (again: the fence and the reduce-scatter follow the keys pass)
+    return MS_OK;
+}
+
 int submit_locked(ms_ctx *c, uint32_t n, const ms_pod_rec *pods, ms_result *results, hipStream_t s) {
     CommState &m = *c->comm;
     HostClock::time_point tp = m.host_prof ? HostClock::now() : HostClock::time_point();
@@ -361,7 +414,8 @@ int submit_locked(ms_ctx *c, uint32_t n, const ms_pod_rec *pods, ms_result *resu
     Batch b{m.order.next_slot(), n, 0, 0, pods, results, nullptr};
     slice_of(m, n, b.first, b.count);
     const uint32_t si = b.slot;
-    int rc = slot_ensure(c, si, cdiv(n, (uint32_t)m.world));
+    const bool nam = c->cfg.plugin_set == MS_PLUGINS_NU_NN_NAM;
+    int rc = slot_ensure(c, si, cdiv(n, (uint32_t)m.world), nam ? nam_shard_classes(c, n) : 0u);
     if (rc) return rc;
     MS_ORD(c, m.order.begin(s, c->order.seq(), co, b.X));
     const hipStream_t X = b.X;
@@ -382,7 +436,7 @@ int submit_locked(ms_ctx *c, uint32_t n, const ms_pod_rec *pods, ms_result *resu
     const int ps = c->cfg.plugin_set;
     // (the sweep event is recorded by the sweep's own dispatch for K1: no
     // separate event packet between consecutive sweeps on X)
-    if (ps != MS_PLUGINS_NU_TT_NN) MS_HIP(c, made(m.order.sweep_event(si).ensure()));
+    if (ps != MS_PLUGINS_NU_TT_NN && !nam) MS_HIP(c, made(m.order.sweep_event(si).ensure()));
     if (co) {  // the stashed batch and this one in one launch
         const Batch b0 = m.stash;
         MS_HIP(c, launch_sweep_pp2(c->t, c->d_cand, c->rows_dev, b0.pods, b0.n, m.slot[b0.slot].keys, pods, n, sl.keys,
@@ -397,6 +451,11 @@ int submit_locked(ms_ctx *c, uint32_t n, const ms_pod_rec *pods, ms_result *resu
         // the two-pass form: this shard's census, every shard's by one all-gather,
         // then this shard's picks for every pod (keys, combined by the reduce-scatter)
         rc = tt2_sharded_sweep(c, b);
+        if (rc) return rc;
+    } else if (nam) {
+        // the same shape with class records: this shard's rescale record per class, every
+        // shard's by one all-gather, then this shard's keys and filter words for every pod
+        rc = nam_sharded_sweep(c, b);
         if (rc) return rc;
     } else {
         rc = sweep_locked(c, n, pods, sl.keys, ps == MS_PLUGINS_NU_NN ? nullptr : sl.flags, X, m.order.sweep_event(si));
@@ -602,6 +661,10 @@ int ms_comm_id_create(ms_comm_id *out) {
     if (r != ncclSuccess) return fail(nullptr, MS_E_RCCL, std::string("ncclGetUniqueId: ") + CCL(ncclGetErrorString)(r));
     std::memcpy(out->internal, &id, sizeof(id));
     return MS_OK;
+}
+
+int ms_comm_plugin_set_supported(int32_t plugin_set) {
+    return plugin_set >= MS_PLUGINS_NU_NN && plugin_set <= MS_PLUGINS_NU_NN_NAM ? 1 : 0;
 }
 
 int ms_comm_init(ms_ctx *c, const ms_comm_id *id, int32_t rank, int32_t world) {

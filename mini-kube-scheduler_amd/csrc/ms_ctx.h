@@ -181,6 +181,12 @@ struct ms_ctx {
     std::vector<ms_nam_required_set> h_req;
     DevBuf<void> d_nam;
     size_t nam_bytes = 0;
+    // d_nam is one scratch for every NAM cycle of the context, as d_tt is: a
+    // cycle on another stream than the previous one waits for ev_nam, recorded
+    // after that one's last launch (two node-sharded submits on different sweep
+    // streams do not follow each other through the context stream)
+    Event ev_nam;
+    hipStream_t nam_stream = nullptr;  // (not owned)
     // node-sharded sequential mode: merged candidate lists (ms_seq_validate_device)
     DevBuf<ms_seq_cand> d_merged;
     DevBuf<uint32_t> d_merged_flags;
@@ -297,6 +303,21 @@ int ensure_tt(ms_ctx *c, size_t need);
 // when that ran on another stream) and releases it after its last.
 int tt_take(ms_ctx *c, hipStream_t s);
 int tt_release(ms_ctx *c, hipStream_t s);
+// The same for d_nam (ev_nam), around every user of the NodeAffinity scratch.
+int nam_take(ms_ctx *c, hipStream_t s);
+int nam_release(ms_ctx *c, hipStream_t s);
+// MS_PLUGINS_NU_NN_NAM over node shards inside the library (ms_comm.cpp): a batch
+// swept whole under ms_nam_layout.h's whole-batch plan. nam_shard_classes: the
+// class records a rank sends for a batch of n_pods (the same on every rank).
+// nam_shard_begin: the scratch for the batch, taken on s. nam_shard_segment: this
+// shard's class records into cls_mine. nam_shard_keys: from the n_shards gathered
+// records, this shard's keys and filter words, resuming from the scratch the
+// segment pass of the same batch left. The caller releases (nam_release) after.
+uint32_t nam_shard_classes(const ms_ctx *c, uint32_t n_pods);
+int nam_shard_begin(ms_ctx *c, uint32_t n_pods, hipStream_t s);
+int nam_shard_segment(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, void *cls_mine, hipStream_t s);
+int nam_shard_keys(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, const void *cls_all, uint32_t n_shards,
+                   uint32_t shard_index, unsigned long long *keys, uint32_t *flags, hipStream_t s);
 
 // ms_seq_host.cpp: the sequential engine's host side
 int ensure_tiles(ms_ctx *c, uint32_t n_tiles);

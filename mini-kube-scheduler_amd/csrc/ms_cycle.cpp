@@ -83,8 +83,8 @@ static NamPlan nam_plan_for(const ms_ctx *c, uint32_t n_pods) {
 
 // Scratch for the plan: its layout's arrays, plus one record (the later shards'
 // table) and one byte (an earlier shard has a non-zero node) per pod of a
-// chunk. Every NAM call runs on the context stream or chains back into it, so
-// one scratch serves them in order.
+// chunk (per class under the whole-batch plan). One scratch serves every NAM
+// call of the context; each takes it on its stream (nam_take / nam_release).
 static int ensure_nam(ms_ctx *c, const NamPlan &plan) {
     const size_t need = plan.alloc;
     if (need <= c->nam_bytes) return MS_OK;
@@ -93,6 +93,60 @@ static int ensure_nam(ms_ctx *c, const NamPlan &plan) {
     c->nam_bytes = 0;
     if (!c->d_nam.alloc(need)) return fail(c, MS_E_OOM, "NodeAffinity scratch");
     c->nam_bytes = need;
+    return MS_OK;
+}
+
+// d_nam is one scratch for every NAM cycle of the context (ms_ctx.h ev_nam): a
+// cycle on another stream than the previous one waits for that one's end.
+int nam_take(ms_ctx *c, hipStream_t s) {
+    MS_HIP(c, made(c->ev_nam.ensure()));
+    if (c->nam_stream && c->nam_stream != s) MS_HIP(c, hipStreamWaitEvent(s, c->ev_nam, 0));
+    return MS_OK;
+}
+
+int nam_release(ms_ctx *c, hipStream_t s) {
+    MS_HIP(c, hipEventRecord(c->ev_nam, s));
+    c->nam_stream = s;
+    return MS_OK;
+}
+
+// The in-library node-sharded cycle (ms_comm.cpp nam_sharded_sweep): the batch
+// as one chunk under the whole-batch plan, one record per class exchanged.
+static NamPlan nam_shard_plan(const ms_ctx *c, uint32_t n_pods) {
+    return nam_plan_whole(c->rows_dev, c->n_terms, n_pods);
+}
+
+uint32_t nam_shard_classes(const ms_ctx *c, uint32_t n_pods) { return nam_class_cap(std::max(1u, n_pods), c->n_terms); }
+
+int nam_shard_begin(ms_ctx *c, uint32_t n_pods, hipStream_t s) {
+    const int rc = ensure_nam(c, nam_shard_plan(c, n_pods));
+    return rc ? rc : nam_take(c, s);
+}
+
+int nam_shard_segment(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, void *cls_mine, hipStream_t s) {
+    const NamPlan plan = nam_shard_plan(c, n_pods);
+    if (c->rows_dev == 0) {  // no rows: identity maps, no non-zero node, no filter bits
+        MS_HIP(c, launch_nam_identity(cls_mine, plan.L.cls_max, s));
+        return MS_OK;
+    }
+    MS_HIP(c, launch_nam_class_segment(c->t, c->rows_dev, d_pods, n_pods, c->d_terms, c->n_terms, plan.L, c->d_nam,
+                                       cls_mine, s));
+    return MS_OK;
+}
+
+int nam_shard_keys(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods, const void *cls_all, uint32_t n_shards,
+                   uint32_t shard_index, unsigned long long *keys, uint32_t *flags, hipStream_t s) {
+    if (c->rows_dev == 0) {  // (as nam_keys_locked: key 0, no filter saw a row)
+        MS_HIP(c, launch_fill_keys(keys, n_pods, 0ull, s));
+        MS_HIP(c, hipMemsetAsync(flags, 0, sizeof(uint32_t) * n_pods, s));
+        return MS_OK;
+    }
+    const NamPlan plan = nam_shard_plan(c, n_pods);
+    char *base = static_cast<char *>(c->d_nam.get());
+    MS_HIP(c, launch_nam_class_keys(c->t, c->rows_dev, d_pods, n_pods, c->d_terms, c->n_terms, seed32_of(c->cfg.seed),
+                                    c->w_nn, c->w_na, cls_all, n_shards, shard_index, c->present_dev ? 1u : 0u, plan.L,
+                                    c->d_nam, base + plan.after, reinterpret_cast<uint8_t *>(base + plan.m_in), keys,
+                                    flags, s));
     return MS_OK;
 }
 
@@ -122,6 +176,8 @@ static int nam_cycle_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods
     const uint32_t B = plan.chunk;
     int rc = ensure_nam(c, plan);
     if (rc) return rc;
+    rc = nam_take(c, s);
+    if (rc) return rc;
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
         rc = nam_keys_locked(c, plan.L, nb, d_pods + s0, nullptr, nullptr, c->d_keys, c->d_flags, s);
@@ -129,7 +185,7 @@ static int nam_cycle_locked(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *d_pods
         MS_HIP(c, launch_decode(d_pods + s0, nb, c->d_keys, c->d_flags, c->present_dev, d_res + s0, s));
         if (commit) MS_HIP(c, launch_apply_binds(c->t, d_pods + s0, nb, d_res + s0, s));
     }
-    return MS_OK;
+    return nam_release(c, s);
 }
 
 // This shard's keys (and filter flags for the resource-aware set) for a batch.
@@ -428,7 +484,9 @@ int ms_nam_segment_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev
     const hipStream_t s = call.stream();
     const NamPlan plan = nam_plan_for(c, n_pods);
     const uint32_t B = plan.chunk;
-    const int rc = ensure_nam(c, plan);
+    int rc = ensure_nam(c, plan);
+    if (rc) return rc;
+    rc = nam_take(c, s);
     if (rc) return rc;
     for (uint32_t s0 = 0; s0 < n_pods; s0 += B) {
         const uint32_t nb = std::min(B, n_pods - s0);
@@ -440,6 +498,8 @@ int ms_nam_segment_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev
         MS_HIP(c, launch_nam_segment(c->t, c->rows_dev, pods_dev + s0, nb, c->d_terms, c->n_terms,
                                      plan.L, c->d_nam, out, s));
     }
+    rc = nam_release(c, s);
+    if (rc) return rc;
     return call.done();
 }
 
@@ -458,6 +518,8 @@ int ms_nam_keys_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, u
     const uint32_t B = plan.chunk;
     int rc = ensure_nam(c, plan);
     if (rc) return rc;
+    rc = nam_take(c, s);
+    if (rc) return rc;
     // the per-pod shard inputs (B records, B bytes) behind the plan layout's scratch
     char *after = static_cast<char *>(c->d_nam.get()) + plan.after;
     uint8_t *m_in = reinterpret_cast<uint8_t *>(static_cast<char *>(c->d_nam.get()) + plan.m_in);
@@ -469,6 +531,8 @@ int ms_nam_keys_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, u
         rc = nam_keys_locked(c, plan.L, nb, pods_dev + s0, after, m_in, keys_dev + s0, nullptr, s);
         if (rc) return rc;
     }
+    rc = nam_release(c, s);
+    if (rc) return rc;
     return call.done();
 }
 

@@ -260,6 +260,8 @@ int ms_schedule_batch_compact(ms_ctx *c, uint32_t n, const ms_pod_compact *pods,
     if (mode != MS_MODE_BATCHED && mode != MS_MODE_SEQUENTIAL) return fail(c, MS_E_INVAL, "unknown mode");
     if (!plugins_stateless(c))
         return fail(c, MS_E_INVAL, "ms_schedule_batch_compact: the resource-aware set needs ms_schedule_batch");
+    if (c->comm && c->cfg.plugin_set == MS_PLUGINS_NU_NN_NAM)  // (as before the in-library NAM cycle: the header's sets only)
+        return fail(c, MS_E_INVAL, "ms_schedule_batch_compact: multi-term NodeAffinity node shards take ms_schedule_batch");
     if (n == 0) return MS_OK;
     std::lock_guard<std::mutex> g(c->sched_mu);
     CallClock ck(c);

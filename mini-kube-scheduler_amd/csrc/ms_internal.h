@@ -228,6 +228,27 @@ hipError_t launch_nam_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec
 // gathered records in[s * stride + p].
 hipError_t launch_nam_flags(const void *in, uint32_t stride, uint32_t n, uint32_t n_pods, uint32_t *flags,
                             hipStream_t s);
+// The in-library node-sharded cycle (ms_comm.cpp), a batch as ONE chunk under a
+// whole-batch plan (nam_plan_whole), exchanging one record per CLASS: class ids
+// are dense in key order from the pods and n_sets alone, so class c is the same
+// class on every shard of a batch.
+// First pass: the class pass (classes, row segments), then this shard's composed
+// record of every class into cls_out (L.cls_max records of MS_NAM_SEG_BYTES;
+// those past the class count are identity records with no bits).
+hipError_t launch_nam_class_segment(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+                                    const void *sets, uint32_t n_sets, const NamLayout &L, void *scratch,
+                                    void *cls_out, hipStream_t s);
+// Second pass, RESUMING from the scratch the first pass of the same batch left
+// (same pods, L and scratch; the class pass is not run again): cls_all holds the
+// n_shards gathered class records [shard][L.cls_max]; after (L.cls_max records)
+// and m_in (L.cls_max bytes) receive, per class, the later shards' composed table
+// and "an earlier shard has a non-zero node"; then keys and flags as launch_nam_keys
+// (flags: this shard's own rows' filter word per pod).
+hipError_t launch_nam_class_keys(const NodeTable &t, uint32_t n_rows, const ms_pod_rec *pods, uint32_t n_pods,
+                                 const void *sets, uint32_t n_sets, uint32_t seed32, uint32_t w_nn, uint32_t w_na,
+                                 const void *cls_all, uint32_t n_shards, uint32_t shard_index, uint32_t listed,
+                                 const NamLayout &L, void *scratch, void *after, uint8_t *m_in,
+                                 unsigned long long *keys, uint32_t *flags, hipStream_t s);
 
 // ---- launchers (ms_kernels.hip) -------------------------------------------
 // All return hipError_t of the launch; none synchronises.

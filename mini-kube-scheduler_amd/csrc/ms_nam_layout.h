@@ -129,4 +129,23 @@ inline NamPlan nam_plan(uint32_t batch_cap, uint32_t n_rows, uint32_t n_sets, ui
     return p;
 }
 
+// The plan of a batch swept WHOLE, as ONE chunk (the in-library node-sharded
+// cycle, ms_comm.cpp): chunk = n_pods and no kNamFBudget shrink, so how a batch
+// is cut never depends on a rank's row count (an allocation too large fails as
+// MS_E_OOM, like any other buffer). The shard inputs behind the scratch are per
+// CLASS: C = nam_class_cap(n_pods, n_sets) records (after) and C bytes (m_in).
+// C = L.cls_max is a function of (n_pods, n_sets) alone: every rank of a
+// communicator computes the same C for a batch, which sizes its all-gather.
+inline NamPlan nam_plan_whole(uint32_t n_rows, uint32_t n_sets, uint32_t n_pods) {
+    NamPlan p;
+    p.chunk = std::max(1u, n_pods);
+    const uint32_t C = nam_class_cap(p.chunk, n_sets);
+    p.L = nam_layout(n_rows, C);
+    const size_t scratch = nam_scratch_bytes(p.L, p.chunk, n_sets);
+    p.after = nam_align(scratch);
+    p.m_in = p.after + (size_t)C * kNamSegBytes;
+    p.alloc = p.m_in + C + 512;
+    return p;
+}
+
 }  // namespace msgpu

@@ -298,6 +298,7 @@ SIGNATURES = {
     "ms_nam_flags_device": (ctypes.c_int, [_vp, _u32, _u32, _vp, _vp, _vp]),
     "ms_comm_id_create": (ctypes.c_int, [ctypes.POINTER(ms_comm_id)]),
     "ms_comm_init": (ctypes.c_int, [_vp, ctypes.POINTER(ms_comm_id), _i32, _i32]),
+    "ms_comm_plugin_set_supported": (ctypes.c_int, [_i32]),
     "ms_sharded_slice": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "ms_sharded_submit": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp]),
     "ms_sharded_drain": (ctypes.c_int, [_vp, _vp]),
@@ -367,6 +368,12 @@ def comm_id_create(lib: Optional[ctypes.CDLL] = None) -> bytes:
     if rc != MS_OK:
         raise MSError("ms_comm_id_create", rc, lib.ms_last_error(None).decode())
     return ctypes.string_at(ctypes.addressof(out), COMM_ID_BYTES)  # (.internal stops at a NUL)
+
+
+def comm_plugin_set_supported(plugin_set: int, lib: Optional[ctypes.CDLL] = None) -> bool:
+    """ms_comm_plugin_set_supported: whether the collective calls of a joined
+    context (comm_init) serve this plugin set. Needs no context and no device."""
+    return bool((lib or load()).ms_comm_plugin_set_supported(int(plugin_set)))
 
 
 def device_count() -> int:

@@ -78,8 +78,11 @@ def flags_op_for(plugin_set: int) -> Optional[str]:
     """How shards combine ms_sweep_device's flags for a plugin set (minisched_gpu.h)."""
     from . import _lib
 
+    # (the TaintToleration and multi-term NodeAffinity sets have no ms_sweep_device form: their
+    # shards exchange summaries / class records, inside the library on a joined engine)
     return {_lib.PLUGINS_NU_NN: None, _lib.PLUGINS_NU_NRF_NN_LA: FLAGS_BYTES,
-            _lib.PLUGINS_NU_NN_NA: FLAGS_U32, _lib.PLUGINS_NU_TT_NN: None}[plugin_set]
+            _lib.PLUGINS_NU_NN_NA: FLAGS_U32, _lib.PLUGINS_NU_TT_NN: None,
+            _lib.PLUGINS_NU_NN_NAM: None}[plugin_set]
 
 
 def combine_scatter_(keys, keys_out, flags=None, flags_out=None, group=None, async_op=False, flags_op=FLAGS_BYTES):
@@ -271,6 +274,14 @@ class ShardedCycle:
                 and not self._library):
             raise ValueError("TaintToleration node shards combine by summaries: join a communicator "
                              "(init_comm) or use ms_tt_summaries_device / ms_tt_decode_device")
+        if engine.plugin_set == _lib.PLUGINS_NU_NN_NAM and split == "nodes":
+            # served by the library on a joined engine (class records all-gathered, keys and
+            # filter bytes reduce-scattered); there is no Python combine for this set
+            if self._library and not _lib.comm_plugin_set_supported(engine.plugin_set, engine.lib):
+                raise ValueError("this library's communicator does not serve the multi-term NodeAffinity set")
+            if world > 1 and not self._library:
+                raise ValueError("multi-term NodeAffinity node shards exchange rescale records: join a "
+                                 "communicator (init_comm) or use ms_nam_segment_device / ms_nam_keys_device")
         if self._library:
             self.a, n_mine = engine.sharded_slice(n_pods)
             self.b = self.a + n_mine
