@@ -71,12 +71,76 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#ifdef MS_PP_TIMELINE
+#include <cstdio>
+#include <vector>
+#endif
 
 #include "ms_device.h"
 
 namespace msgpu {
 
 namespace {
+
+// Diagnostic build (`make pp-timeline`, -DMS_PP_TIMELINE): a wave timeline of
+// k_sweep_nunn_pp. Lane 0 of every wave writes s_memtime at the points below
+// into tl[workgroup][wave][stamp] (plain vector stores; a kernel argument that
+// exists in this build only), and one pair of s_memrealtime (100 MHz) for the
+// clock. sweep_pp_impl allocates the buffer, and appends it after a synchronise
+// to the file named by MS_PP_TIMELINE (read out by tools/pp_wg_timeline.py).
+// Without the macro every MS_TL* below expands to nothing.
+#ifdef MS_PP_TIMELINE
+constexpr uint32_t kTlStamps = 48;  // u64 per wave
+enum : uint32_t {
+    kTlEntry = 0,      // kernel entry
+    kTlBar1 = 1,       // after the sort's barriers 1 .. 3 (0: an unsorted chunk has none)
+    kTlBar2 = 2,
+    kTlBar3 = 3,
+    kTlPlanes = 4,     // the plane loads landed (0: the workgroup loads none)
+    kTlBar4 = 5,       // after the barrier in front of the sweep
+    kTlSweepEnd = 6,   // the wave's sweep done
+    kTlSweepBar = 7,   // after the sweep's barrier
+    kTlFinal = 8,      // after the lane table's final pass and its barrier
+    kTlEnd = 9,        // the wave's end
+    kTlReal0 = 10,     // s_memrealtime at entry and at the end
+    kTlReal1 = 11,
+    kTlDigit0 = 12,    // per sort slot s / 2, three each: its (last pass's) tile loads issued,
+                       // the tiles landed (first hash can issue), the digit done
+    kTlHashes = 42,    // candidate hashes per lane of the wave: sum of pods x tiles x 3
+};
+#define MS_TL_KPARAM , u64 *__restrict__ tl
+#define MS_TL_PARAM , u64 *tlw
+#define MS_TL_PASS , tlw
+#define MS_TL_NONE , (u64 *)nullptr
+#define MS_TL_BUF , tl_dev
+#define MS_TL_INIT                                                                                      \
+    u64 *tlw = tl ? tl + ((size_t)blockIdx.x * kPpMaxWaves + wv) * kTlStamps : nullptr;                   \
+    MS_TL(kTlEntry);                                                                                    \
+    MS_TL_PUT(kTlReal0, __builtin_amdgcn_s_memrealtime())
+#define MS_TL_PUT(i, v)                  \
+    do {                                 \
+        const u64 tl_v_ = (v);           \
+        if (tlw && lane == 0u) tlw[i] = tl_v_; \
+    } while (0)
+#define MS_TL(i) MS_TL_PUT(i, __builtin_amdgcn_s_memtime())
+#define MS_TL_LANDED __builtin_amdgcn_s_waitcnt(0x0F70)  // s_waitcnt vmcnt(0)
+#define MS_TL_COUNT_DECL u64 tl_hashes = 0
+#define MS_TL_COUNT(n) tl_hashes += (n)
+#define MS_TL_COUNT_PUT MS_TL_PUT(kTlHashes, tl_hashes)
+#else
+#define MS_TL_KPARAM
+#define MS_TL_PARAM
+#define MS_TL_PASS
+#define MS_TL_NONE
+#define MS_TL_BUF
+#define MS_TL_INIT
+#define MS_TL_PUT(i, v)
+#define MS_TL(i)
+#define MS_TL_LANDED
+#define MS_TL_COUNT_DECL
+#define MS_TL_COUNT(n)
+#define MS_TL_COUNT_PUT
+#endif
 
 template <typename F>
 constexpr uint32_t truth3(F f) {  // v_bitop3 table, S0 the most significant index bit
@@ -468,6 +532,12 @@ struct ClassLanes {
     u64 planes;
 };
 
+// (pods: the lane's class holds a pod)
+__device__ __forceinline__ u64 plane_classes(const DigitLists &L, uint32_t lane, bool pods) {
+    const uint32_t c = min(lane, kPpClasses);
+    return __ballot(lane <= kPpClasses && pods && (c == kPpClasses || list_tiles(L, (c & 1u) != 0u) == 0u));
+}
+
 __device__ __forceinline__ ClassLanes class_lanes(const uint32_t *hdr, const uint32_t *rb, uint32_t base10,
                                                   uint32_t lane) {
     const uint32_t c = min(lane, kPpClasses);
@@ -475,9 +545,18 @@ __device__ __forceinline__ ClassLanes class_lanes(const uint32_t *hdr, const uin
     C.beg = rb[c];
     C.end = rb[c + 1];
     C.L = digit_lists(hdr, ((c >> 1) + base10) % kCandDigits);
-    C.planes = __ballot(lane <= kPpClasses && C.beg < C.end &&
-                        (c == kPpClasses || list_tiles(C.L, (c & 1u) != 0u) == 0u));
+    C.planes = plane_classes(C.L, lane, C.beg < C.end);
     return C;
+}
+
+// class_lanes' planes from the sort's class counts (cnt, final after its second
+// barrier), before the bounds exist. Every wave reads the same words, so the answer
+// is workgroup-uniform. Empty (config C: every class has tiles and every pod a
+// digit): nothing of this workgroup is taken from the planes.
+__device__ __forceinline__ u64 plane_classes_ahead(const uint32_t *hdr, const uint32_t *cnt, uint32_t base10,
+                                                   uint32_t lane) {
+    const uint32_t c = min(lane, kPpClasses);
+    return plane_classes(digit_lists(hdr, ((c >> 1) + base10) % kCandDigits), lane, cnt[c] != 0u);
 }
 
 // A pod of class c (pod_class) of a list-form chunk is swept by sweep_lists: the
@@ -623,7 +702,8 @@ __device__ __forceinline__ void load_list_tiles(const uint32_t *__restrict__ can
 template <int LT>
 __device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, const ClassLanes &C,
                                             const uint2 *pinfo, uint32_t wv, uint32_t waves, uint32_t lane,
-                                            u64 *lds, uint32_t *tabl) {
+                                            u64 *lds, uint32_t *tabl MS_TL_PARAM) {
+    MS_TL_COUNT_DECL;
     for (uint32_t s = 0; s < kPpClasses; s += 2) {
         const uint32_t b0 = lane_value(C.beg, s), b1 = lane_value(C.end, s), b2 = lane_value(C.end, s + 1u);
         if (b0 >= b2) continue;
@@ -634,10 +714,16 @@ __device__ __forceinline__ void sweep_lists(const uint32_t *__restrict__ cand, c
             const uint32_t ns = t0 < L.ns ? min((uint32_t)kPpWords, (L.ns - t0 + waves - 1u) / waves) : 0u;
             uint32_t B[3 * kPpWords];
             load_list_tiles(cand, L.off, t0, nt, waves, lane, B);
+            MS_TL(kTlDigit0 + 3u * (s >> 1));
+            MS_TL_LANDED;
+            MS_TL(kTlDigit0 + 3u * (s >> 1) + 1u);
+            MS_TL_COUNT(3u * ((b0 < b1 ? ns * (b1 - b0) : 0u) + nt * (b2 - b1)));
             if (ns != 0u && b0 < b1) sweep_list_tiles<LT>(ns, B, pinfo, b0, b1, lane, lds, tabl);
             if (b1 < b2) sweep_list_tiles<LT>(nt, B, pinfo, b1, b2, lane, lds, tabl);
         }
+        MS_TL(kTlDigit0 + 3u * (s >> 1) + 2u);
     }
+    MS_TL_COUNT_PUT;
 }
 
 // One wave sweeps the chunk's pods [0, np). runs: the entries are class-sorted
@@ -744,7 +830,7 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     const ms_pod_rec *__restrict__ pods1, uint32_t n_pods1, uint32_t chunk, uint32_t seed32, u64 *__restrict__ keys1,
     int atomic_keys, ms_result *__restrict__ results, uint32_t present, NodeTable tab, int commit,
     uint32_t pstride, ms_result_compact *__restrict__ resc, PpJob2 j2, int fix_ok, uint32_t xtra,
-    const uint32_t *__restrict__ cand) {
+    const uint32_t *__restrict__ cand MS_TL_KPARAM) {
     // LDS: one combine slot per pod of the chunk, then the chunk's pod entries,
     // then the kPpSortWords words of the class sort, then (LT != 0) the lane
     // table: LT words per pod position
@@ -753,6 +839,7 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
     uint2 *pinfo = reinterpret_cast<uint2 *>(lds + chunk + (xtra ? 8u : 0u));
     const uint32_t lane = lane_id();
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    MS_TL_INIT;
     const bool second = j2.pods && blockIdx.x >= j2.nblk1;  // (workgroup-uniform)
     const ms_pod_rec *__restrict__ pods = second ? j2.pods : pods1;
     const uint32_t n_pods = second ? j2.n_pods : n_pods1;
@@ -774,6 +861,9 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
         uint4 *z = reinterpret_cast<uint4 *>(ltab);
         for (uint32_t i = threadIdx.x; i < np * (LT / 4); i += blockDim.x) z[i] = make_uint4(0u, 0u, 0u, 0u);
     }
+    // a list-form workgroup with no class to take from the planes (plane_classes_ahead)
+    // clears this: it loads no plane and runs no sweep_range
+    bool use_planes = true;
     if (!runs) {
         for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
             lds[i] = 0;
@@ -788,12 +878,16 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
         if (lists)
             for (uint32_t i = threadIdx.x; i <= kCandClasses; i += blockDim.x) hdr[i] = cand[i];
         __syncthreads();
+        MS_TL(kTlBar1);
         for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
             uint2 e = pod_entry(pods, pbeg + i, seed32, pstride, node_base % 10u);
             e.y |= atomicAdd(&cnt[pod_class(e.y)], 1u) << 21;
             reinterpret_cast<uint2 *>(lds)[i] = e;
         }
         __syncthreads();
+        MS_TL(kTlBar2);
+        if constexpr (KW == kPpWords)
+            if (lists) use_planes = plane_classes_ahead(hdr, cnt, node_base % 10u, lane) != 0ull;
         if (threadIdx.x <= kPpClasses) {
             // region A: the whole 8-pod blocks of the digit classes (the list form: all
             // their pods); region B: the rest
@@ -812,6 +906,7 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
             sb[threadIdx.x] = na + b;
         }
         __syncthreads();
+        MS_TL(kTlBar3);
         for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
             const uint2 e = reinterpret_cast<const uint2 *>(lds)[i];
             const uint32_t c = pod_class(e.y), rank = e.y >> 21;
@@ -822,96 +917,112 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
         }
     }
 
-    // the wave's groups, dealt round-robin over the workgroup's waves so their
-    // word counts differ by at most one: word k of lane l is group
-    // g0 + (k * waves + wv) * 64 + l. The workgroup's last word, when it holds
-    // T <= 32 groups, is packed instead (sweep_range): its wave loads group
-    // (lane mod 64/tpt) of it into Wt.
     const uint32_t waves = blockDim.x >> 6;
-    const uint32_t g0 = blockIdx.y * waves * 64u * KW;
-    const uint32_t ng = min(n_groups - g0, waves * 64u * KW);  // (blockIdx.y < gy: g0 < n_groups)
-    const uint32_t wlast = (ng + 63u) / 64u - 1u, tail_n = ng - wlast * 64u;
-    uint32_t tpt = TP ? tail_pods(ng, waves) : 0u;
-    const uint32_t wv_t = wlast % waves, tshare = min(kTailShare, waves - wv_t);  // its waves
-    const bool owner = wv == wv_t;     // it is this wave's last word in the dealing
-    if (wv < wv_t || wv >= wv_t + tshare) tpt = 0u;  // wave-uniform
-    Word W[KW], Wt;
-    int nw = 0;
-    bool over = false, misaligned = false;
+    // The planes, for everything but a list-form workgroup none of whose classes is
+    // taken from them. Such a workgroup works out no word's share (tail_pods, a loop of
+    // divisions, stood between every workgroup's sort and its first hash), loads no
+    // plane and no packed last word, detects no mode and has no sweep_range to run:
+    // it goes from the scatter's barrier straight to sweep_lists. (The test is
+    // workgroup-uniform, so every wave meets the same barrier.)
+    if (use_planes) {
+        // the wave's groups, dealt round-robin over the workgroup's waves so their
+        // word counts differ by at most one: word k of lane l is group
+        // g0 + (k * waves + wv) * 64 + l. The workgroup's last word, when it holds
+        // T <= 32 groups, is packed instead (sweep_range): its wave loads group
+        // (lane mod 64/tpt) of it into Wt.
+        const uint32_t g0 = blockIdx.y * waves * 64u * KW;
+        const uint32_t ng = min(n_groups - g0, waves * 64u * KW);  // (blockIdx.y < gy: g0 < n_groups)
+        const uint32_t wlast = (ng + 63u) / 64u - 1u, tail_n = ng - wlast * 64u;
+        uint32_t tpt = TP ? tail_pods(ng, waves) : 0u;
+        const uint32_t wv_t = wlast % waves, tshare = min(kTailShare, waves - wv_t);  // its waves
+        const bool owner = wv == wv_t;     // it is this wave's last word in the dealing
+        if (wv < wv_t || wv >= wv_t + tshare) tpt = 0u;  // wave-uniform
+        Word W[KW], Wt;
+        int nw = 0;
+        bool over = false, misaligned = false;
 #pragma unroll
-    for (int k = 0; k < KW; ++k) {
-        const uint32_t wi = k * waves + wv;
-        const uint32_t gw = g0 + wi * 64u;
-        const uint32_t g = gw + lane;
-        const bool in = g < n_groups && !(tpt && owner && wi == wlast);
-        if (gw < n_groups && !(tpt && owner && wi == wlast)) nw = k + 1;  // wave-uniform
-        W[k].d0 = in ? planes[kPlaneD0 * gstride + g] : 0u;
-        W[k].d1 = in ? planes[kPlaneD1 * gstride + g] : 0u;
-        W[k].d2 = in ? planes[kPlaneD2 * gstride + g] : 0u;
-        W[k].d3 = in ? planes[kPlaneD3 * gstride + g] : 0u;
-        W[k].sched = in ? planes[kPlaneSched * gstride + g] : 0u;
-        W[k].pres = in ? planes[kPlanePresent * gstride + g] : 0u;
-        W[k].dsched = in ? planes[kPlaneDigitSched * gstride + g] : 0u;
-        W[k].dpres = in ? planes[kPlaneDigitPres * gstride + g] : 0u;
-        W[k].hb = (node_base + g * kGroupRows) * kG24;
-        const uint32_t ov = in ? planes[kPlaneOver * gstride + g] : 0u;
-        // more than 3 present rows of one digit in a group: the fast slots cannot hold them
-        over = over || (ov & 1u) != 0u;
-        misaligned = misaligned || (ov & 2u) != 0u;
-    }
-    {
-        const uint32_t gi = tpt ? lane & ((64u / tpt) - 1u) : 0u;
-        const uint32_t g = g0 + wlast * 64u + gi;
-        const bool in = tpt && gi < tail_n;
-        Wt.d0 = in ? planes[kPlaneD0 * gstride + g] : 0u;
-        Wt.d1 = in ? planes[kPlaneD1 * gstride + g] : 0u;
-        Wt.d2 = in ? planes[kPlaneD2 * gstride + g] : 0u;
-        Wt.d3 = in ? planes[kPlaneD3 * gstride + g] : 0u;
-        Wt.sched = in ? planes[kPlaneSched * gstride + g] : 0u;
-        Wt.pres = in ? planes[kPlanePresent * gstride + g] : 0u;
-        Wt.hb = (node_base + g * kGroupRows) * kG24;
-        Wt.dsched = Wt.dpres = 0u;  // (the packed word always takes word_fast / word_scan)
-        over = over || (in && (planes[kPlaneOver * gstride + g] & 1u) != 0u);
-    }
-    const bool gen = __ballot(over) != 0;
-    // every word of the wave digit-aligned
-    const int mode = gen ? kModeGen : (fix_ok && __ballot(misaligned) == 0) ? kModeFix : kModeFast;
-    __syncthreads();
-    if (np && (nw || tpt)) {
-        switch (nw * 6 + mode * 2 + (tpt ? 1 : 0)) {  // wave-uniform
+        for (int k = 0; k < KW; ++k) {
+            const uint32_t wi = k * waves + wv;
+            const uint32_t gw = g0 + wi * 64u;
+            const uint32_t g = gw + lane;
+            const bool in = g < n_groups && !(tpt && owner && wi == wlast);
+            if (gw < n_groups && !(tpt && owner && wi == wlast)) nw = k + 1;  // wave-uniform
+            W[k].d0 = in ? planes[kPlaneD0 * gstride + g] : 0u;
+            W[k].d1 = in ? planes[kPlaneD1 * gstride + g] : 0u;
+            W[k].d2 = in ? planes[kPlaneD2 * gstride + g] : 0u;
+            W[k].d3 = in ? planes[kPlaneD3 * gstride + g] : 0u;
+            W[k].sched = in ? planes[kPlaneSched * gstride + g] : 0u;
+            W[k].pres = in ? planes[kPlanePresent * gstride + g] : 0u;
+            W[k].dsched = in ? planes[kPlaneDigitSched * gstride + g] : 0u;
+            W[k].dpres = in ? planes[kPlaneDigitPres * gstride + g] : 0u;
+            W[k].hb = (node_base + g * kGroupRows) * kG24;
+            const uint32_t ov = in ? planes[kPlaneOver * gstride + g] : 0u;
+            // more than 3 present rows of one digit in a group: the fast slots cannot hold them
+            over = over || (ov & 1u) != 0u;
+            misaligned = misaligned || (ov & 2u) != 0u;
+        }
+        {
+            const uint32_t gi = tpt ? lane & ((64u / tpt) - 1u) : 0u;
+            const uint32_t g = g0 + wlast * 64u + gi;
+            const bool in = tpt && gi < tail_n;
+            Wt.d0 = in ? planes[kPlaneD0 * gstride + g] : 0u;
+            Wt.d1 = in ? planes[kPlaneD1 * gstride + g] : 0u;
+            Wt.d2 = in ? planes[kPlaneD2 * gstride + g] : 0u;
+            Wt.d3 = in ? planes[kPlaneD3 * gstride + g] : 0u;
+            Wt.sched = in ? planes[kPlaneSched * gstride + g] : 0u;
+            Wt.pres = in ? planes[kPlanePresent * gstride + g] : 0u;
+            Wt.hb = (node_base + g * kGroupRows) * kG24;
+            Wt.dsched = Wt.dpres = 0u;  // (the packed word always takes word_fast / word_scan)
+            over = over || (in && (planes[kPlaneOver * gstride + g] & 1u) != 0u);
+        }
+        const bool gen = __ballot(over) != 0;
+        // every word of the wave digit-aligned
+        const int mode = gen ? kModeGen : (fix_ok && __ballot(misaligned) == 0) ? kModeFix : kModeFast;
+        MS_TL_LANDED;
+        MS_TL(kTlPlanes);
+        __syncthreads();
+        MS_TL(kTlBar4);
+        if (np && (nw || tpt)) {
+            switch (nw * 6 + mode * 2 + (tpt ? 1 : 0)) {  // wave-uniform
 #define MS_PP_CASE1(N, M, T)                                                                                     \
-    case 6 * N + 2 * M + T:                                                                                      \
-        if constexpr (N <= KW && (N > 0 || T))                                                                   \
-            sweep_range<KW, (N <= KW ? N : KW), M, T>(W, Wt, tpt, tshare, wv - wv_t, pinfo, rb, runs, lists, hdr,   \
-                                                      node_base % 10u, np, lane, lds);                          \
-        break;
+        case 6 * N + 2 * M + T:                                                                                      \
+            if constexpr (N <= KW && (N > 0 || T))                                                                   \
+                sweep_range<KW, (N <= KW ? N : KW), M, T>(W, Wt, tpt, tshare, wv - wv_t, pinfo, rb, runs, lists, hdr,   \
+                                                          node_base % 10u, np, lane, lds);                          \
+            break;
 #define MS_PP_CASE(N)        \
-    MS_PP_CASE1(N, 0, false) \
-    MS_PP_CASE1(N, 0, true)  \
-    MS_PP_CASE1(N, 1, false) \
-    MS_PP_CASE1(N, 1, true)  \
-    MS_PP_CASE1(N, 2, false) \
-    MS_PP_CASE1(N, 2, true)
-            MS_PP_CASE(0)
-            MS_PP_CASE(1)
-            MS_PP_CASE(2)
-            MS_PP_CASE(3)
-            MS_PP_CASE(4)
-            MS_PP_CASE(5)
-            MS_PP_CASE(6)
-            MS_PP_CASE(7)
-            MS_PP_CASE(8)
+        MS_PP_CASE1(N, 0, false) \
+        MS_PP_CASE1(N, 0, true)  \
+        MS_PP_CASE1(N, 1, false) \
+        MS_PP_CASE1(N, 1, true)  \
+        MS_PP_CASE1(N, 2, false) \
+        MS_PP_CASE1(N, 2, true)
+                MS_PP_CASE(0)
+                MS_PP_CASE(1)
+                MS_PP_CASE(2)
+                MS_PP_CASE(3)
+                MS_PP_CASE(4)
+                MS_PP_CASE(5)
+                MS_PP_CASE(6)
+                MS_PP_CASE(7)
+                MS_PP_CASE(8)
 #undef MS_PP_CASE
 #undef MS_PP_CASE1
-            default:
-                break;  // no groups in this wave
+                default:
+                    break;  // no groups in this wave
+            }
         }
+    } else {
+        __syncthreads();
+        MS_TL(kTlBar4);
     }
     if constexpr (KW == kPpWords)
         if (np && lists)
             sweep_lists<LT>(cand, class_lanes(hdr, rb, node_base % 10u, lane), pinfo, wv, waves, lane, lds,
-                            ltab + lane);
+                            ltab + lane MS_TL_PASS);
+    MS_TL(kTlSweepEnd);
     __syncthreads();
+    MS_TL(kTlSweepBar);
     if constexpr (LT != 0) {
         // The lane table's final pass, once per pod: LT / 4 lanes to a row. A list-form
         // maximum is level 11 whatever its value (0 is a real candidate's hash), so what
@@ -930,6 +1041,7 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
             }
         }
         __syncthreads();
+        MS_TL(kTlFinal);
     }
     for (uint32_t i = threadIdx.x; i < np; i += blockDim.x) {
         const u64 v = lds[i];
@@ -969,6 +1081,8 @@ __global__ __launch_bounds__(64 * kPpMaxWaves) void k_sweep_nunn_pp(
             }
         }
     }
+    MS_TL(kTlEnd);
+    MS_TL_PUT(kTlReal1, __builtin_amdgcn_s_memrealtime());
 }
 
 __host__ __device__ inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -1264,7 +1378,7 @@ hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_ro
                            chunk * (sizeof(u64) + sizeof(uint2)) + kPpSortWords * sizeof(uint32_t), s, t.planes,
                            t.gcap, n_groups, t.base, pods, n_pods, chunk, seed32, keys, 1, (ms_result *)nullptr, present,
                            t, 0, (uint32_t)sizeof(ms_pod_rec), (ms_result_compact *)nullptr, PpJob2{}, fix_ok, 0u,
-                           (const uint32_t *)nullptr);
+                           (const uint32_t *)nullptr MS_TL_NONE);
         e = hipGetLastError();
         if (e == hipSuccess && results) e = launch_decode(pods, n_pods, keys, nullptr, present, results, s);
         if (e == hipSuccess && results && commit) e = launch_apply_binds(t, pods, n_pods, results, s);
@@ -1281,10 +1395,27 @@ hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_ro
     // (gy == 1: the workgroup holds every group; the 8-word form stays unpacked: its
     // packed instantiation needs 117 VGPRs, half the waves per SIMD it sizes for)
     const bool tp = KW == (uint32_t)kPpWords && tail_pods(n_groups, W) != 0u;
+#ifdef MS_PP_TIMELINE
+    // (diagnostic build, one launching thread: the buffer is kept between launches)
+    static u64 *tl_dev = nullptr;
+    static size_t tl_cap = 0;
+    const size_t tl_n = (size_t)grid.x * kPpMaxWaves * kTlStamps;
+    if (tl_n > tl_cap) {
+        if (tl_dev) (void)hipFree(tl_dev);
+        tl_dev = nullptr, tl_cap = 0;
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&tl_dev), tl_n * sizeof(u64));
+        if (e != hipSuccess) return e;
+        tl_cap = tl_n;
+    }
+    {
+        const hipError_t e = hipMemsetAsync(tl_dev, 0, tl_n * sizeof(u64), s);
+        if (e != hipSuccess) return e;
+    }
+#endif
 #define MS_PP_LAUNCH(KWV, TPV, LTV)                                                                                 \
     hipExtLaunchKernelGGL((k_sweep_nunn_pp<KWV, TPV, LTV>), grid, dim3(64 * W), lds, s, nullptr, done, 0, t.planes,   \
                           t.gcap, n_groups, t.base, pods, n_pods, chunk, seed32, kk, 0, results, present, t, cm, pstride, \
-                          resc, j2, fix_ok, xtra, cand)
+                          resc, j2, fix_ok, xtra, cand MS_TL_BUF)
     if (KW == (uint32_t)kPpWordsSmall) {
         MS_PP_LAUNCH(kPpWordsSmall, false, 0);
     } else if (table) {
@@ -1299,6 +1430,23 @@ hipError_t sweep_pp_impl(const NodeTable &t, const uint32_t *cand, uint32_t n_ro
         else MS_PP_LAUNCH(kPpWords, false, 0);
     }
 #undef MS_PP_LAUNCH
+#ifdef MS_PP_TIMELINE
+    if (const char *path = getenv("MS_PP_TIMELINE")) {
+        // one record per launch, appended: 8 header words, then grid.x x 16 x kTlStamps u64
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        std::vector<u64> host(tl_n);
+        e = hipMemcpy(host.data(), tl_dev, tl_n * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        if (FILE *f = fopen(path, "ab")) {
+            const uint32_t hdr[8] = {0x4C545050u /* "PPTL" */, 1u, grid.x, W, kTlStamps, chunk, n_pods, (uint32_t)kPpMaxWaves};
+            fwrite(hdr, sizeof(hdr), 1, f);
+            fwrite(host.data(), sizeof(u64), tl_n, f);
+            fclose(f);
+        }
+    }
+#endif
     return hipGetLastError();
 }
 }  // namespace
