@@ -513,6 +513,61 @@ int ms_nam_flags_device(ms_ctx *ctx, uint32_t n_pods, uint32_t n_shards, const v
 int ms_schedule_sequential_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev,
                                   ms_result *results_dev, void *stream);
 
+/* ---- explain: per-node filter verdicts and plugin scores of a pod's cycle ----
+ * What the reference's result store keeps per pod and node
+ * (scheduler/plugin/resultstore/store.go: each filter plugin's verdict, each
+ * score plugin's raw and final score) and RunFilterPlugins' NodeToStatusMap, for
+ * n_pods pods against a window [first, first + n_nodes) of global ordinals. The
+ * node table is as it stands after the queued deltas are drained; every pod is
+ * judged against the same state and nothing is committed (MS_MODE_BATCHED
+ * without binds, as ms_select_batch_device). DESIGN.md §2 "Explain".
+ *
+ * One row per (pod, node of the window), pod-major. A row is scored only when
+ * the node passed every filter and the pod's name ends in a digit: a filtered or
+ * absent node has key, raw and weighted all 0 (the reference scores feasible
+ * nodes only), and so has every row of a non-digit pod (its Score fails on the
+ * first node, nodenumber.go:74-77), whose status stays exact. */
+#define MS_EXPLAIN_ABSENT 0xFFu
+typedef struct ms_explain_row {   /* 24 bytes */
+    uint64_t key;        /* the packed selectHost key of this pair, global ordinal; 0 unless scored */
+    uint16_t raw[2];     /* [0] NodeNumber, [1] the set's second score plugin: LeastAllocated (set 1),
+                            NodeAffinity (2, 4), TaintToleration (3); 0 for set 0. As Score() returned it. */
+    uint16_t weighted[2];/* the result store's "finalscore": after the in-loop NormalizeScore hook has run
+                            over the pod's whole feasible list, times the plugin weight (ms_config.score_weight
+                            for sets 2 and 4, else 1). weighted[0] + weighted[1] == key >> 52. */
+    uint8_t  status;     /* 0: passed every filter; MS_MASK_* bit of the FIRST failing filter plugin
+                            (minisched.go:130-137); MS_EXPLAIN_ABSENT: not in the LIST (tombstone / never upserted) */
+    uint8_t  _pad[7];    /* zero */
+} ms_explain_row;
+/* One summary per pod, over the WHOLE table (not the window):
+ * present == feasible + the sum of rejected[]; with feasible == 0 the set bits
+ * {i : rejected[i] > 0} are ms_result.plugin_mask; best_key decodes to the node
+ * and score the scheduling calls return for the pod. */
+typedef struct ms_explain_summary {  /* 32 bytes */
+    uint32_t present;      /* nodes in the LIST */
+    uint32_t feasible;     /* F */
+    uint32_t rejected[4];  /* nodes whose first failing plugin is bit i of MS_MASK_* (NU, NRF, TT, NA) */
+    uint64_t best_key;     /* max key over all scored rows of the table, 0 if none: selectHost */
+} ms_explain_summary;
+/* ms_explain_device: device pointers, `stream` as for the other device entry
+ * points (ordered like them; nothing is synchronised). rows_dev: n_pods x
+ * n_nodes rows, or NULL (then the window is ignored); summaries_dev: n_pods, or
+ * NULL; not both NULL. All five plugin sets; set 4 uses the registered preferred
+ * and required tables. n_pods > MS_EXPLAIN_MAX_PODS or both outputs NULL:
+ * MS_E_INVAL; a window outside [node_base, node_base + max_nodes): MS_E_CAPACITY;
+ * n_pods == 0: MS_OK. A context joined to a communicator is refused
+ * (MS_E_INVAL): the other shards' LIST context would be needed.
+ * ms_explain: the same on host arrays (a diagnostic path: the pods go in chunks
+ * whose device staging of rows stays within 64 MiB, plain copies on the context
+ * stream, synchronised before it returns).
+ * Additive to ABI 7 (MS_ABI_VERSION unchanged): a caller detects the feature by
+ * the symbol ms_explain_device. */
+#define MS_EXPLAIN_MAX_PODS 256u
+int ms_explain_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev, uint32_t first, uint32_t n_nodes,
+                      ms_explain_row *rows_dev, ms_explain_summary *summaries_dev, void *stream);
+int ms_explain(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods, uint32_t first, uint32_t n_nodes,
+               ms_explain_row *rows, ms_explain_summary *summaries);
+
 /* ---- multi-GPU inside the library: one RCCL communicator per job ------------
  * One process (or host thread) per GPU, one context per rank, each owning the
  * contiguous node shard [node_base, node_base + max_nodes) of the cluster's

@@ -190,6 +190,14 @@ struct ms_ctx {
     // node-sharded sequential mode: merged candidate lists (ms_seq_validate_device)
     DevBuf<ms_seq_cand> d_merged;
     DevBuf<uint32_t> d_merged_flags;
+    // explain (ms_explain_host.cpp): the three stages' scratch (explain_bytes
+    // allocated; every explain call is an OrderedCall, so the context stream
+    // orders its users), and ms_explain's device staging of pods and rows
+    DevBuf<void> d_explain;
+    size_t explain_bytes = 0;
+    DevBuf<ms_pod_rec> d_ex_pods;  // MS_EXPLAIN_MAX_PODS records
+    DevBuf<ms_explain_row> d_ex_rows;
+    size_t ex_rows_cap = 0;
 
     // every access to the table or the scratch above, on whichever stream, is
     // ordered through the context stream (ms_order.h; OrderedCall below)

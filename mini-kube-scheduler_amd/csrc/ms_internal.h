@@ -465,6 +465,31 @@ hipError_t launch_tt_combine(const void *in, uint32_t stride, uint32_t n_segs, c
                              uint32_t seed32, void *out, ms_result *results, const NodeTable &t, int commit,
                              hipStream_t s);
 
+// ---- explain (ms_explain.hip): per-node verdicts and scores ---------------
+// Rows per tile of the explain kernels (one row per thread of a workgroup).
+constexpr uint32_t kExplainTile = 256;
+struct ExplainArgs {
+    NodeTable t;
+    uint32_t n_rows = 0;   // sweep extent of the table (rows past it are absent)
+    int32_t plugin_set = 0;
+    const ms_pod_rec *pods = nullptr;
+    uint32_t n_pods = 0;
+    uint32_t seed32 = 0, w_nn = 1, w_na = 1;
+    const void *sets = nullptr;  // MS_PLUGINS_NU_NN_NAM: the NamTab of every registered id
+    uint32_t n_sets = 0;
+    uint32_t win_lo = 0, win_n = 0;  // the window in local rows (rows != nullptr)
+    ms_explain_row *rows = nullptr;  // n_pods x win_n, or null
+    bool summaries = false;          // whole-table summaries (with best_key) into explain_summaries(scratch)
+    void *scratch = nullptr;         // explain_scratch_bytes
+};
+// Local rows the call's tiles cover and the scratch they need.
+uint32_t explain_extent(uint32_t n_rows, uint32_t win_lo, uint32_t win_n, bool rows);
+size_t explain_scratch_bytes(int32_t plugin_set, uint32_t extent, uint32_t n_pods);
+// Where the n_pods summaries of a call lie inside its scratch.
+ms_explain_summary *explain_summaries(void *scratch);
+// Tile summaries, the per-pod scan over the tiles, then the rows (and the best keys).
+hipError_t launch_explain(const ExplainArgs &a, hipStream_t s);
+
 // ---- launchers (ms_kernels.hip), continued: decodes, binds, read-back ------
 // One launch decoding several batches' pod slices, each with a device-side present flag.
 constexpr uint32_t kMaxSliceJobs = 8;

@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "ms_device.h"
+#include "ms_tt_closed.h"
 
 namespace msgpu {
 
@@ -82,7 +83,7 @@ __device__ __forceinline__ void tt_merge_into(TtSummary &r, const TtSummary &b) 
     if (b.n == 0u) r.last = alast;
 }
 
-__device__ __forceinline__ int32_t tt_map(int32_t m, int32_t v) { return m == 0 ? 100 : 100 - (100 * v) / m; }
+// (tt_map, one step of the hook: ms_tt_closed.h)
 
 // Final TaintToleration scores and selectHost over the merged summary of every
 // segment of the cluster, in LIST order (oracle/ms_oracle.c tt_closed).
@@ -292,14 +293,8 @@ __global__ void k_tt_combine(const TtSummary *__restrict__ in, uint32_t stride, 
 constexpr uint32_t kTt2Planes = 24;
 enum : uint32_t { kPlPres = 0, kPlUns = 1, kPlHard = 2, kPlSoft = 10, kPlDigit = 18, kPlNz = 22 };
 constexpr uint32_t kTt2Threads = 256;  // pods per census / pick workgroup (lane = pod)
-constexpr uint32_t kEntNone = 0xFFFFFFFFu;
 
-struct TtCensus {  // 32 B per (segment, pod)
-    uint32_t n, flags;
-    uint32_t occ, occ1;  // bit 2c + q: a middle row of class (c, q) / one matching NodeNumber
-    uint32_t first[3], last;  // entries: ordinal | nn << 21 | c << 24 (kEntNone: none)
-};
-static_assert(sizeof(TtCensus) == MS_TT_CENSUS_BYTES, "TtCensus layout (ms_tt_census_device)");
+// (TtCensus, 32 B per (segment, pod), its entries ent_* and kEntNone: ms_tt_closed.h)
 struct TtPlan {  // 32 B per pod
     uint32_t mode;  // 0: the plan kernel wrote the result, 1: pick
     uint32_t score; // S*
@@ -308,11 +303,6 @@ struct TtPlan {  // 32 B per pod
     u64 best;       // best explicit entry at S* (make_key), 0: none
 };
 static_assert(sizeof(TtPlan) == MS_TT_CENSUS_BYTES, "plans buffers are sized in census records (ms_comm.cpp)");
-
-__device__ __forceinline__ uint32_t ent_pack(uint32_t row, uint32_t c, uint32_t nn) { return row | nn << 21 | c << 24; }
-__device__ __forceinline__ uint32_t ent_row(uint32_t e) { return e & 0x1FFFFFu; }
-__device__ __forceinline__ uint32_t ent_nn(uint32_t e) { return (e >> 21) & 1u; }
-__device__ __forceinline__ uint32_t ent_cc(uint32_t e) { return (e >> 24) & 0xFu; }
 
 template <typename F>
 constexpr uint32_t truth3(F f) {  // v_bitop3 table, S0 the most significant index bit
@@ -425,10 +415,6 @@ __device__ __forceinline__ uint32_t tt_c_at(const TtWord &w, uint32_t b) {
     return ((w.c0 >> b) & 1u) | ((w.c1 >> b) & 1u) << 1 | ((w.c2 >> b) & 1u) << 2 | ((w.c3 >> b) & 1u) << 3;
 }
 
-__device__ __forceinline__ uint32_t swap_parity(uint32_t occ) {  // 18 class bits: 2c <-> 2c + 1
-    return ((occ & 0x15555u) << 1) | ((occ >> 1) & 0x15555u);
-}
-
 // grid (pod blocks, segments of seg_words words): lane = pod.
 __global__ __launch_bounds__(kTt2Threads) void k_tt2_census(const uint32_t *__restrict__ planes, uint32_t n_words,
                                                             uint32_t seg_words, const ms_pod_rec *__restrict__ pods,
@@ -513,32 +499,7 @@ __global__ __launch_bounds__(kTt2Threads) void k_tt2_census(const uint32_t *__re
     out[(size_t)blockIdx.y * n_pods + p] = o;
 }
 
-// r <- r merged with b (b follows r in LIST order), occupancy form of tt_merge_into.
-__device__ __forceinline__ void tt2_merge(TtCensus &r, const TtCensus &b) {
-    const uint32_t an = r.n, alast = r.last;
-    r.n = an + b.n;
-    r.flags |= b.flags;
-    const bool sh = (an & 1u) != 0;
-    r.occ |= sh ? swap_parity(b.occ) : b.occ;
-    r.occ1 |= sh ? swap_parity(b.occ1) : b.occ1;
-    auto place = [&](uint32_t e, uint32_t g) {
-        if (g == 0u) r.first[0] = e;
-        if (g == 1u) r.first[1] = e;
-        if (g == 2u) r.first[2] = e;
-        if (g + 1u == r.n) r.last = e;
-        if (g >= 3u && g + 1u < r.n) {
-            const uint32_t k = 1u << (2u * ent_cc(e) + (g & 1u));
-            r.occ |= k;
-            if (ent_nn(e)) r.occ1 |= k;
-        }
-    };
-    if (an > 3u) place(alast, an - 1u);
-    if (b.n > 0u) place(b.first[0], an);
-    if (b.n > 1u) place(b.first[1], an + 1u);
-    if (b.n > 2u) place(b.first[2], an + 2u);
-    if (b.n > 3u) place(b.last, an + b.n - 1u);
-    if (b.n == 0u) r.last = alast;
-}
+// (tt2_merge, the occupancy form of tt_merge_into: ms_tt_closed.h)
 
 __device__ __forceinline__ void tt2_store(ms_result *results, uint32_t p, const ms_result &res, const NodeTable &t,
                                           const ms_pod_rec &pod, int commit) {

@@ -103,6 +103,14 @@ SEQ_CAND = np.dtype(
     ]
 )
 SEQ_TOPK = 4
+# ms_explain_row / ms_explain_summary: the row view of a pod's cycle (Engine.explain)
+EXPLAIN_ROW = np.dtype([("key", "<u8"), ("raw", "<u2", (2,)), ("weighted", "<u2", (2,)), ("status", "u1"),
+                        ("_pad", "u1", (7,))])
+EXPLAIN_SUMMARY = np.dtype([("present", "<u4"), ("feasible", "<u4"), ("rejected", "<u4", (4,)), ("best_key", "<u8")])
+assert EXPLAIN_ROW.itemsize == 24 and EXPLAIN_SUMMARY.itemsize == 32
+EXPLAIN_ABSENT = 0xFF  # MS_EXPLAIN_ABSENT
+EXPLAIN_MAX_PODS = 256  # MS_EXPLAIN_MAX_PODS
+EXPLAIN_TILE = 256  # rows per tile of the explain kernels (csrc/ms_internal.h kExplainTile)
 TT_SUMMARY_BYTES = 192  # MS_TT_SUMMARY_BYTES
 TT_CENSUS_BYTES = 32  # MS_TT_CENSUS_BYTES
 NAM_SEG_BYTES = 104  # MS_NAM_SEG_BYTES
@@ -283,6 +291,8 @@ SIGNATURES = {
     "ms_apply_binds_device": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp]),
     "ms_schedule_sequential_device": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp]),
     "ms_select_batch_device": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp]),
+    "ms_explain_device": (ctypes.c_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "ms_explain": (ctypes.c_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp]),
     "ms_seq_candidates_device": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
     "ms_seq_validate_device": (ctypes.c_int, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "ms_tt_summaries_device": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp]),
@@ -532,6 +542,30 @@ class Engine:
             "ms_select_batch_device",
             self.lib.ms_select_batch_device(self.h, n_pods, pods_dev, results_dev, stream or None),
         )
+
+    def explain(self, pods: np.ndarray, first: Optional[int] = None, n_nodes: Optional[int] = None,
+                rows: bool = True, summaries: bool = True):
+        """ms_explain: per (pod, node of the window [first, first + n_nodes)) the
+        filter verdict, raw and final plugin scores and the selectHost key, and per
+        pod the whole-table summary; nothing is committed. The window defaults to
+        the context's whole node range. Returns (rows[n_pods, n_nodes] of
+        EXPLAIN_ROW, summaries[n_pods] of EXPLAIN_SUMMARY); rows=False or
+        summaries=False passes NULL for that output and returns None in its place."""
+        p = np.ascontiguousarray(pods, dtype=POD_REC)
+        first = self.node_base if first is None else int(first)
+        n_nodes = self.node_base + self.max_nodes - first if n_nodes is None else int(n_nodes)
+        r = np.zeros((len(p), n_nodes), dtype=EXPLAIN_ROW) if rows else None
+        s = np.zeros(len(p), dtype=EXPLAIN_SUMMARY) if summaries else None
+        self._check("ms_explain", self.lib.ms_explain(self.h, len(p), _ptr(p), first, n_nodes if rows else 0, _ptr(r),
+                                                      _ptr(s)))
+        return r, s
+
+    def explain_device(self, n_pods, pods_dev, first, n_nodes, rows_dev, summaries_dev, stream=0):
+        """ms_explain_device on device-resident pods: rows_dev (n_pods x n_nodes
+        EXPLAIN_ROW) or 0, summaries_dev (n_pods EXPLAIN_SUMMARY) or 0."""
+        self._check("ms_explain_device",
+                    self.lib.ms_explain_device(self.h, n_pods, pods_dev, first, n_nodes, rows_dev or None,
+                                               summaries_dev or None, stream or None))
 
     def seq_candidates_device(self, n_pods, pods_dev, cands_dev, flags_dev, stream=0):
         """Node-sharded sequential mode, step 1: this shard's top-4 candidates + flags."""

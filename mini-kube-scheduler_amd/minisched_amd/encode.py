@@ -566,3 +566,69 @@ class DigitOrdinals:
         self.live = max(0, self.live - 1)
         if 0 <= digit <= 9 and self.count[digit]:
             self.count[digit] -= 1
+
+
+# ---- explain: the result store's annotations and the FitError line -------------
+# The reference's scheduler/plugin/resultstore/store.go keeps, per pod, three maps
+# node name -> plugin name -> string and publishes each as one JSON annotation:
+# the filter result ("passed", or the reason of the plugin that rejected the node;
+# RunFilterPlugins stops at the first failure, so later plugins have no entry), the
+# score as Score() returned it, and the final score (normalised, times the plugin
+# weight). Engine.explain's rows carry exactly that, per plugin set.
+PASSED_FILTER_MESSAGE = "passed"  # store.go PassedFilterMessage
+# filter plugins in the order minisched runs them, as bit i of MS_MASK_*
+FILTER_PLUGIN_NAMES = ("NodeUnschedulable", "NodeResourcesFit", "TaintToleration", "NodeAffinity")
+# k8s v1.22 reasons: nodeunschedulable.ErrReasonUnschedulable, tainttoleration.ErrReasonNotMatch,
+# nodeaffinity.ErrReasonPod. NodeResourcesFit reports one reason per short resource
+# ("Insufficient cpu", "Insufficient memory", "Too many pods"); a row records the
+# plugin only, so its reason names the three.
+FILTER_REASONS = (
+    "node(s) were unschedulable",
+    "Insufficient cpu, memory or pods",
+    "node(s) had taints that the pod didn't tolerate",
+    "node(s) didn't match Pod's node affinity/selector",
+)
+_EXPLAIN_FILTERS = {0: (0,), 1: (0, 1), 2: (0,), 3: (0, 2), 4: (0, 3)}  # plugin set -> filter bits, in order
+_EXPLAIN_SCORES = {0: ("NodeNumber",), 1: ("NodeNumber", "NodeResourcesLeastAllocated"),
+                   2: ("NodeNumber", "NodeAffinity"), 3: ("NodeNumber", "TaintToleration"),
+                   4: ("NodeNumber", "NodeAffinity")}
+_EXPLAIN_ABSENT = 0xFF
+
+
+def explain_annotations(rows, node_names, plugin_set: int):
+    """One pod's explain rows (EXPLAIN_ROW, one per name of node_names) as the result
+    store's three maps (filter, score, finalscore): node -> plugin -> string.
+    A node that is not in the LIST has no entry; a filtered node has filter entries
+    up to and including the plugin that rejected it and no score; a pod whose
+    name does not end in a digit has no scores at all (its rows are unscored)."""
+    if len(rows) != len(node_names):
+        raise ValueError("one row per node name")
+    filt: Dict[str, Dict[str, str]] = {}
+    score: Dict[str, Dict[str, str]] = {}
+    final: Dict[str, Dict[str, str]] = {}
+    bits = _EXPLAIN_FILTERS[plugin_set]
+    plugins = _EXPLAIN_SCORES[plugin_set]
+    for row, name in zip(rows, node_names):
+        st = int(row["status"])
+        if st == _EXPLAIN_ABSENT:
+            continue
+        f = filt.setdefault(name, {})
+        for b in bits:
+            if st == 1 << b:
+                f[FILTER_PLUGIN_NAMES[b]] = FILTER_REASONS[b]
+                break
+            f[FILTER_PLUGIN_NAMES[b]] = PASSED_FILTER_MESSAGE
+        if st != 0 or int(row["key"]) == 0:
+            continue
+        score[name] = {p: str(int(row["raw"][k])) for k, p in enumerate(plugins)}
+        final[name] = {p: str(int(row["weighted"][k])) for k, p in enumerate(plugins)}
+    return filt, score, final
+
+
+def fit_error_message(summary) -> str:
+    """framework.FitError.Error() (k8s v1.22 framework/types.go) from one
+    EXPLAIN_SUMMARY: "0/N nodes are available: <count> <reason>, ...", the reasons
+    sorted as strings, N the nodes in the LIST."""
+    rej = [int(x) for x in summary["rejected"]]
+    reasons = sorted(f"{n} {FILTER_REASONS[b]}" for b, n in enumerate(rej) if n)
+    return f"0/{int(summary['present'])} nodes are available: {', '.join(reasons)}."
