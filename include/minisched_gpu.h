@@ -556,7 +556,8 @@ typedef struct ms_explain_summary {  /* 32 bytes */
  * and required tables. n_pods > MS_EXPLAIN_MAX_PODS or both outputs NULL:
  * MS_E_INVAL; a window outside [node_base, node_base + max_nodes): MS_E_CAPACITY;
  * n_pods == 0: MS_OK. A context joined to a communicator is refused
- * (MS_E_INVAL): the other shards' LIST context would be needed.
+ * (MS_E_INVAL): the other shards' LIST context would be needed; such a context
+ * is served by the collective ms_explain_sharded_device / ms_explain_sharded below.
  * ms_explain: the same on host arrays (a diagnostic path: the pods go in chunks
  * whose device staging of rows stays within 64 MiB, plain copies on the context
  * stream, synchronised before it returns).
@@ -650,6 +651,55 @@ int ms_sharded_slice(const ms_ctx *ctx, uint32_t n_pods, uint32_t *first, uint32
 int ms_sharded_submit(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev, ms_result *results_dev,
                       void *stream);
 int ms_sharded_drain(ms_ctx *ctx, void *stream);
+
+/* Explain on node shards: ms_explain_device / ms_explain over the cluster's LIST
+ * (the shards in rank order, which is ordinal order), on contexts joined to a
+ * communicator. COLLECTIVE: every rank calls with the same pods in the same
+ * order (and so the same n_pods); the window and the two outputs are each
+ * rank's own business.
+ *   rows: the window [first, first + n_nodes) of global ordinals inside this
+ *   rank's own range [node_base, node_base + max_nodes). Every field of
+ *   ms_explain_row means what it means on one context, over the cluster's LIST:
+ *   weighted[] is the final score after the in-loop hook has run over the pod's
+ *   whole feasible list of the cluster, key the r3 key with the global ordinal;
+ *   status, raw and the zero rules for filtered, absent and non-digit-pod rows
+ *   are unchanged. rows may be NULL or n_nodes 0.
+ *   summaries: over the whole cluster, identical on every rank: present,
+ *   feasible and rejected[] summed over the shards, best_key the maximum over
+ *   the shards; it decodes to what ms_schedule_batch on the joined contexts
+ *   returns for the pod. May be NULL, and both outputs may be NULL: the rank
+ *   then only takes part in the exchange (a rank that wants nothing must still
+ *   call).
+ * Per call and rank: one all-gather of n_pods opaque per-shard records (the
+ * shard's counts, NodeAffinity anchor, TaintToleration census and composed
+ * rescale table: a shard is one more tile of the single-context stages) and one
+ * of n_pods uint64 best keys, both sized by n_pods alone and both always issued
+ * when n_pods > 0, on `stream` after the sharded pipeline is drained onto it.
+ * All five plugin sets; set 4 under the contract that every rank registers the
+ * same tables (ms_comm_init above). Nothing is committed; the node table is as
+ * it stands after the queued deltas are drained.
+ * The argument checks run before any collective: a context not joined to a
+ * communicator: MS_E_INVAL (checked first; ms_explain / ms_explain_device serve
+ * it); n_pods > MS_EXPLAIN_MAX_PODS: MS_E_INVAL; a window outside the context's
+ * range: MS_E_CAPACITY; n_pods == 0: MS_OK with no collective. CALLER
+ * OBLIGATION: a rank whose arguments fail issues no collective, so the ranks of
+ * one call must pass arguments that fail or pass alike, as every rank submits
+ * the same batches. A RUNTIME failure on one rank after the checks (MS_E_HIP,
+ * MS_E_OOM, MS_E_RCCL; the scratch is allocated before the first collective)
+ * may leave that rank short of a collective its peers have issued or will
+ * issue: as for the collective scheduling calls, the communicator is then
+ * unusable and the job's contexts are to be destroyed.
+ * ms_explain_sharded: the same on host arrays; the exchange runs once for all
+ * pods and only the rows are staged in pod chunks (ms_explain's 64 MiB rule), so
+ * a rank's window never changes the collectives.
+ * Additive to ABI 7 (MS_ABI_VERSION unchanged): a caller detects the feature by
+ * the symbol ms_explain_sharded_device. */
+int ms_explain_sharded_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev,
+                              uint32_t first, uint32_t n_nodes,
+                              ms_explain_row *rows_dev, ms_explain_summary *summaries_dev, void *stream);
+int ms_explain_sharded(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods,
+                       uint32_t first, uint32_t n_nodes,
+                       ms_explain_row *rows, ms_explain_summary *summaries);
 
 #ifdef __cplusplus
 }

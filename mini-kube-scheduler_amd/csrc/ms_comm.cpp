@@ -561,6 +561,13 @@ int comm_fence_reads(ms_ctx *c, hipStream_t writer) {
     return fenced;
 }
 
+int comm_drain_to(ms_ctx *c, hipStream_t s) { return drain_to(c, s); }
+
+int comm_all_gather(ms_ctx *c, const void *send, void *recv, size_t bytes, hipStream_t s) {
+    MS_NCCL(c, CCL(ncclAllGather)(send, recv, bytes, ncclUint8, c->comm->comm, s));
+    return MS_OK;
+}
+
 void comm_free(ms_ctx *c) {
     delete c->comm;
     c->comm = nullptr;

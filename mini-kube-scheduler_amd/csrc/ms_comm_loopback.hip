@@ -235,12 +235,19 @@ ncclResult_t lb_ncclCommDestroy(ncclComm_t comm) {
     Comm *c = reinterpret_cast<Comm *>(comm);
     if (!c) return ncclInvalidArgument;
     {
-        std::lock_guard<std::mutex> lk(c->g->mu);
-        (void)hipEventSynchronize(c->g->ev_done[c->rank]);
-        (void)hipEventDestroy(c->g->ev_send[c->rank]);
-        (void)hipEventDestroy(c->g->ev_done[c->rank]);
-        c->g->ev_send[c->rank] = c->g->ev_done[c->rank] = nullptr;
-        ++c->g->left;
+        // The events go with the LAST rank that leaves, not with their own rank: after the
+        // second barrier of a collective a slower rank still makes its stream wait on every
+        // rank's done event (collective(), last loop, outside the mutex), while a faster one
+        // may already have returned from the call and be destroying its context.
+        Group &g = *c->g;
+        std::lock_guard<std::mutex> lk(g.mu);
+        (void)hipEventSynchronize(g.ev_done[c->rank]);
+        if (++g.left == (g.solo ? 1 : g.world))
+            for (int j = 0; j < kMaxRanks; ++j) {
+                if (g.ev_send[j]) (void)hipEventDestroy(g.ev_send[j]);
+                if (g.ev_done[j]) (void)hipEventDestroy(g.ev_done[j]);
+                g.ev_send[j] = g.ev_done[j] = nullptr;
+            }
     }
     delete c;  // the group goes with its last shared_ptr
     return ncclSuccess;

@@ -352,5 +352,9 @@ void comm_rank_world(const ms_ctx *c, int32_t *rank, int32_t *world);
 // communicator's internal streams; returns 1 if it inserted waits, 0 if none
 // were outstanding (or no communicator), < 0 on failure.
 int comm_fence_reads(ms_ctx *c, hipStream_t writer);
+// The sharded pipeline drained onto s (everything pending decoded, s after the
+// decode stream), as the collective cycles do before they use s for their own
+// collectives (the caller holds sched_mu).
+int comm_drain_to(ms_ctx *c, hipStream_t s);
 
 }  // namespace msgpu

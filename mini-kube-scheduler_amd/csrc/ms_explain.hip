@@ -32,7 +32,15 @@
 // The pair evaluation of the resource-aware set is the sweep's general form
 // (ms_rows.h eval_full: int64 LeastAllocated with an exact compare), not the
 // binary64 shortcut.
+//
+// On node shards (ms_explain_sharded_device) a shard is one more tile: k_ex_shard
+// reduces a pod's tile records to one ExShard record, the records of all shards
+// are all-gathered by the host layer, k_ex_scan_seeded is the scan started from
+// them, k_ex_rows runs unchanged, and after a second all-gather of the shards'
+// best keys k_ex_best_shards takes their maximum. No kernel waits on a value
+// another rank wrote: all cross-rank ordering comes from the collectives.
 #include <algorithm>
+#include <cstddef>
 
 #include "ms_device.h"
 #include "ms_nam_device.h"
@@ -466,6 +474,223 @@ __global__ __launch_bounds__(64) void k_ex_best(uint32_t n_tiles, const u64 *__r
     if (lane == 0) sums[p].best_key = m;
 }
 
+// ---- node shards (minisched_gpu.h ms_explain_sharded_device) ---------------
+// A shard is one more tile: per pod it hands the other shards one record of what
+// its tiles hand k_ex_scan, each part associative and in LIST order (the shards
+// in rank order). The records of all G shards are gathered shard-major
+// (all[s * n_pods + p]); k_ex_scan_seeded is k_ex_scan started from them. The
+// layout is internal: the host layer moves the records as bytes.
+struct ExShard {  // 168 B per (shard, pod), the same for every set
+    uint32_t present, feasible, rej[4];
+    uint32_t anchor;  // sets 2, 4: the shard's anchor as a GLOBAL ordinal (kRowNone: none)
+    uint32_t _pad;
+    TtCensus census;  // set 3: the shard's tiles merged (tt2_merge; its entries hold global ordinals)
+    NamSeg seg;       // set 4: the shard's composed rescale table, its "any" and filter bits
+};
+static_assert(sizeof(ExShard) == 168 && sizeof(ExShard) % 8 == 0 && offsetof(ExShard, seg) % 4 == 0,
+              "ExShard is gathered as bytes and its table copied as words");
+
+// U <- U o T on the wave's LDS table (k_ex_scan's step): entries lane, lane + 64.
+__device__ __forceinline__ void table_compose(uint8_t *tab, const uint8_t *T, uint32_t lane) {
+    const uint32_t v0 = lane, v1 = lane + 64u;
+    const uint8_t a = tab[T[v0]];
+    const uint8_t b = v1 <= 100u ? tab[T[v1]] : 0;
+    wave_lds_sync();
+    tab[v0] = a;
+    if (v1 <= 100u) tab[v1] = b;
+    wave_lds_sync();
+}
+
+// One wave per pod: the shard's record from its tiles' records (mine[p]).
+template <int kSet>
+__global__ __launch_bounds__(64) void k_ex_shard(uint32_t n_tiles, uint32_t node_base,
+                                                 const ExTile *__restrict__ tiles,
+                                                 const TtCensus *__restrict__ census,
+                                                 const NamSeg *__restrict__ segs, ExShard *__restrict__ mine) {
+    __shared__ __attribute__((aligned(16))) uint8_t tab[MS_NAM_SEG_BYTES];
+    __shared__ TtCensus cs[64];
+    const uint32_t p = blockIdx.x, lane = threadIdx.x;
+    const size_t at0 = (size_t)p * n_tiles;
+    uint32_t present = 0, feasible = 0, rej[4] = {0, 0, 0, 0}, anchor_inv = 0, bits = 0;
+    TtCensus merged = {};
+    for (uint32_t b0 = 0; b0 < n_tiles; b0 += 64u) {
+        const uint32_t i = b0 + lane;
+        ExTile x = {};
+        x.anchor = kRowNone;
+        if (i < n_tiles) x = tiles[at0 + i];
+        present += x.present;
+        feasible += x.feasible;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rej[k] += x.rej[k];
+        anchor_inv = max(anchor_inv, ~x.anchor);
+        if (kSet == MS_PLUGINS_NU_NN_NAM && i < n_tiles) {
+            const NamSeg *T = segs + at0 + i;
+            bits |= (T->any ? 1u : 0u) | (T->_pad[0] ? 2u : 0u) | (T->_pad[1] ? 4u : 0u);
+        }
+        if (kSet == MS_PLUGINS_NU_TT_NN) {  // as k_ex_scan: 64 records staged, merged in LIST order by one lane
+            if (i < n_tiles) cs[lane] = census[at0 + i];
+            wave_lds_sync();
+            if (lane == 0) {
+                const uint32_t n = min(64u, n_tiles - b0);
+                for (uint32_t k = 0; k < n; ++k) {
+                    if (b0 + k == 0u) merged = cs[0];
+                    else tt2_merge(merged, cs[k]);
+                }
+            }
+            wave_lds_sync();
+        }
+    }
+    present = wave_sum_u32_dpp(present);
+    feasible = wave_sum_u32_dpp(feasible);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rej[k] = wave_sum_u32_dpp(rej[k]);
+    const uint32_t anchor = ~wave_max_u32_dpp(anchor_inv);
+    uint32_t *seg_out = reinterpret_cast<uint32_t *>(&mine[p].seg);
+    if (kSet == MS_PLUGINS_NU_NN_NAM) {
+        // k_ex_scan's descending composition taken one step further, through tile 0. The "any" and
+        // filter bits are carried so that the record is a whole NamSeg of the shard, as a tile's is
+        // of the tile; the seeded scan and the rows read T[0..100] only.
+        const bool any = __ballot(bits & 1u) != 0ull, f_nu = __ballot(bits & 2u) != 0ull,
+                   f_na = __ballot(bits & 4u) != 0ull;
+        if (lane == 0) table_identity(tab);
+        wave_lds_sync();
+        for (uint32_t tile = n_tiles; tile-- > 0u;) {
+            const NamSeg *T = segs + at0 + tile;
+            if (T->T[100] == 100 || tab[100] == 0) continue;  // (the identity; all 0 stays all 0)
+            table_compose(tab, T->T, lane);
+        }
+        if (lane == 0) {
+            tab[101] = any ? 1 : 0;
+            tab[102] = f_nu ? 1 : 0;
+            tab[103] = f_na ? 1 : 0;
+        }
+        wave_lds_sync();
+        if (lane < MS_NAM_SEG_BYTES / 4u) seg_out[lane] = reinterpret_cast<const uint32_t *>(tab)[lane];
+    } else if (lane < MS_NAM_SEG_BYTES / 4u) {
+        seg_out[lane] = 0u;  // (no table in this set: the record's bytes stay defined)
+    }
+    if (lane != 0) return;
+    ExShard &o = mine[p];
+    o.present = present;
+    o.feasible = feasible;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o.rej[k] = rej[k];
+    o.anchor = anchor == kRowNone ? kRowNone : node_base + anchor;
+    o._pad = 0;
+    o.census = merged;  // (all zero outside set 3)
+}
+
+// k_ex_scan for one shard of G (`shard`), started from the G gathered records
+// instead of from nothing: a tile's rank base begins at the feasible count of the
+// earlier shards, the plan comes from every shard's census merged in rank order
+// (the same on every rank), the anchor is the cluster's least anchor ordinal (a
+// local row only on the shard that holds it), after[] begins at the later
+// shards' tables composed (ranks descending), and the summary counts are the
+// sums over the shards. best_key is left 0 (k_ex_best_shards).
+template <int kSet>
+__global__ __launch_bounds__(64) void k_ex_scan_seeded(uint32_t n_tiles, uint32_t n_pods, uint32_t n_shards,
+                                                       uint32_t shard, uint32_t node_base, uint32_t n_local,
+                                                       const ExShard *__restrict__ all,
+                                                       const ExTile *__restrict__ tiles,
+                                                       const NamSeg *__restrict__ segs, uint32_t *__restrict__ base,
+                                                       NamSeg *__restrict__ after, ExPlan *__restrict__ plans,
+                                                       ms_explain_summary *__restrict__ sums) {
+    __shared__ __attribute__((aligned(16))) uint8_t tab[MS_NAM_SEG_BYTES];
+    const uint32_t p = blockIdx.x, lane = threadIdx.x;
+    const size_t at0 = (size_t)p * n_tiles;
+    // the shards' counts: one shard per lane and round
+    uint32_t present = 0, feasible = 0, before = 0, rej[4] = {0, 0, 0, 0}, anchor_min = kRowNone;
+    for (uint32_t s0 = 0; s0 < n_shards; s0 += 64u) {
+        const uint32_t s = s0 + lane;
+        if (s >= n_shards) continue;
+        const ExShard &x = all[(size_t)s * n_pods + p];
+        present += x.present;
+        feasible += x.feasible;
+        before += s < shard ? x.feasible : 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rej[k] += x.rej[k];
+        anchor_min = min(anchor_min, x.anchor);
+    }
+    present = wave_sum_u32_dpp(present);
+    feasible = wave_sum_u32_dpp(feasible);
+    before = wave_sum_u32_dpp(before);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rej[k] = wave_sum_u32_dpp(rej[k]);
+    anchor_min = ~wave_max_u32_dpp(~anchor_min);  // the least ordinal: the first in LIST order
+    // the rank base of this shard's tiles: the earlier shards' feasible rows, then the in-shard prefix
+    uint32_t run = before;
+    for (uint32_t b0 = 0; b0 < n_tiles; b0 += 64u) {
+        const uint32_t i = b0 + lane;
+        const uint32_t f = i < n_tiles ? tiles[at0 + i].feasible : 0u;
+        uint32_t inc = f;  // inclusive scan over the lanes
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t v = (uint32_t)__shfl_up((int)inc, off, 64);
+            if (lane >= off) inc += v;
+        }
+        if (i < n_tiles) base[at0 + i] = run + inc - f;
+        run += (uint32_t)__shfl((int)inc, 63, 64);
+    }
+    if (kSet == MS_PLUGINS_NU_NN_NAM) {
+        // after[tile] = the rescales of every LATER tile and shard composed: the later shards'
+        // tables first (ranks descending to shard + 1), then this shard's tiles descending
+        if (lane == 0) table_identity(tab);
+        wave_lds_sync();
+        for (uint32_t s = n_shards; s-- > shard + 1u;) {
+            const NamSeg *T = &all[(size_t)s * n_pods + p].seg;
+            if (T->T[100] == 100 || tab[100] == 0) continue;
+            table_compose(tab, T->T, lane);
+        }
+        for (uint32_t tile = n_tiles; tile-- > 0u;) {
+            if (lane < MS_NAM_SEG_BYTES / 4u)
+                reinterpret_cast<uint32_t *>(after + at0 + tile)[lane] = reinterpret_cast<const uint32_t *>(tab)[lane];
+            const NamSeg *T = segs + at0 + tile;
+            if (T->T[100] == 100 || tab[100] == 0) continue;
+            table_compose(tab, T->T, lane);
+        }
+    }
+    if (lane != 0) return;
+    ExPlan plan = {};
+    plan.F = feasible;
+    const uint32_t a = anchor_min - node_base;  // (wraps past n_local below this shard's range)
+    plan.anchor = (anchor_min != kRowNone && anchor_min >= node_base && a < n_local) ? a : kRowNone;
+    if (kSet == MS_PLUGINS_NU_TT_NN) {
+        TtCensus merged = all[p].census;
+        for (uint32_t s = 1; s < n_shards; ++s) tt2_merge(merged, all[(size_t)s * n_pods + p].census);
+        ex_tt_plan(merged, plan);
+    }
+    plans[p] = plan;
+    ms_explain_summary o;
+    o.present = present;
+    o.feasible = feasible;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o.rejected[k] = rej[k];
+    o.best_key = 0;
+    sums[p] = o;
+}
+
+// One wave per pod: this shard's best key (k_ex_best's maximum) into best[p].
+__global__ __launch_bounds__(64) void k_ex_best_shard(uint32_t n_tiles, const u64 *__restrict__ tile_best,
+                                                      u64 *__restrict__ best) {
+    const uint32_t p = blockIdx.x, lane = threadIdx.x;
+    u64 m = 0;
+    for (uint32_t i = lane; i < n_tiles; i += 64u) m = umax64(m, tile_best[(size_t)p * n_tiles + i]);
+    m = wave_max_u64(m);
+    if (lane == 0) best[p] = m;
+}
+
+// One thread per pod: best_key = the maximum of the G gathered shard maxima
+// (the keys embed the global ordinal: selectHost over the union of the shards).
+__global__ __launch_bounds__(256) void k_ex_best_shards(uint32_t n_pods, uint32_t n_shards,
+                                                        const u64 *__restrict__ best_all,
+                                                        ms_explain_summary *__restrict__ sums) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pods) return;
+    u64 m = 0;
+    for (uint32_t s = 0; s < n_shards; ++s) m = umax64(m, best_all[(size_t)s * n_pods + p]);
+    sums[p].best_key = m;
+}
+
 inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -477,10 +702,13 @@ struct ExScratch {
     u64 *tile_best;
     TtCensus *census;
     NamSeg *segs, *after;
+    // node shards (n_shards > 0): the G gathered records and best keys, shard-major
+    ExShard *shard_all;
+    u64 *best_all;
     size_t bytes;
 };
 
-ExScratch ex_layout(void *scratch, int32_t plugin_set, uint32_t extent, uint32_t n_pods) {
+ExScratch ex_layout(void *scratch, int32_t plugin_set, uint32_t extent, uint32_t n_pods, uint32_t n_shards = 0) {
     const size_t cells = (size_t)cdiv(std::max(extent, 1u), kExThreads) * std::max(n_pods, 1u);
     char *b = static_cast<char *>(scratch);
     size_t o = 0;
@@ -498,6 +726,10 @@ ExScratch ex_layout(void *scratch, int32_t plugin_set, uint32_t extent, uint32_t
     x.census = reinterpret_cast<TtCensus *>(take(plugin_set == MS_PLUGINS_NU_TT_NN ? cells * sizeof(TtCensus) : 0));
     x.segs = reinterpret_cast<NamSeg *>(take(plugin_set == MS_PLUGINS_NU_NN_NAM ? cells * sizeof(NamSeg) : 0));
     x.after = reinterpret_cast<NamSeg *>(take(plugin_set == MS_PLUGINS_NU_NN_NAM ? cells * sizeof(NamSeg) : 0));
+    // (after everything else: the single-context layout is the prefix)
+    const size_t gathered = (size_t)n_shards * std::max(n_pods, 1u);
+    x.shard_all = reinterpret_cast<ExShard *>(take(gathered * sizeof(ExShard)));
+    x.best_all = reinterpret_cast<u64 *>(take(gathered * 8));
     x.bytes = o;
     return x;
 }
@@ -530,6 +762,47 @@ hipError_t launch_set(const ExplainArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// The tiles a sharded call covers: the whole table always (the best keys), and the window.
+inline uint32_t shard_extent(const ExplainArgs &a) { return explain_extent(a.n_rows, a.win_lo, a.win_n, true); }
+
+template <int kSet>
+hipError_t launch_shard_set(const ExplainArgs &a, ExplainShardStage stage, uint32_t p0, uint32_t nb, hipStream_t s) {
+    const uint32_t extent = shard_extent(a);
+    const uint32_t n_tiles = cdiv(extent, kExThreads);
+    const ExScratch x = ex_layout(a.scratch, kSet, extent, a.n_pods, a.n_shards);
+    const NamTab *sets = static_cast<const NamTab *>(a.sets);
+    ExShard *mine = x.shard_all + (size_t)a.shard * a.n_pods;
+    u64 *best_mine = x.best_all + (size_t)a.shard * a.n_pods;
+    switch (stage) {
+        case kExShardRecords:
+            hipLaunchKernelGGL(k_ex_tiles<kSet>, dim3(n_tiles, a.n_pods), dim3(kExThreads), 0, s, a.t, a.n_rows, n_tiles,
+                               a.pods, a.seed32, sets, a.n_sets, x.tiles, x.census, x.segs);
+            hipLaunchKernelGGL(k_ex_shard<kSet>, dim3(a.n_pods), dim3(64), 0, s, n_tiles, a.t.base, x.tiles, x.census,
+                               x.segs, mine);
+            break;
+        case kExShardScan:
+            hipLaunchKernelGGL(k_ex_scan_seeded<kSet>, dim3(a.n_pods), dim3(64), 0, s, n_tiles, a.n_pods, a.n_shards,
+                               a.shard, a.t.base, a.n_rows, x.shard_all, x.tiles, x.segs, x.base, x.after, x.plans,
+                               x.sums);
+            break;
+        case kExShardRows: {  // pods [p0, p0 + nb): every tile (the best keys), the window's rows into a.rows
+            const size_t c0 = (size_t)p0 * n_tiles;
+            hipLaunchKernelGGL(k_ex_rows<kSet>, dim3(n_tiles, nb), dim3(kExThreads), 0, s, a.t, a.n_rows, n_tiles, 0u,
+                               a.pods + p0, a.seed32, a.w_nn, a.w_na, sets, a.n_sets, x.base + c0, x.after + c0,
+                               x.plans + p0, x.tile_best + c0, a.win_n ? a.rows : nullptr, a.win_lo, a.win_n);
+            break;
+        }
+        case kExShardBest:
+            hipLaunchKernelGGL(k_ex_best_shard, dim3(a.n_pods), dim3(64), 0, s, n_tiles, x.tile_best, best_mine);
+            break;
+        case kExShardMax:
+            hipLaunchKernelGGL(k_ex_best_shards, dim3(cdiv(a.n_pods, 256u)), dim3(256), 0, s, a.n_pods, a.n_shards,
+                               x.best_all, x.sums);
+            break;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
 
 uint32_t explain_extent(uint32_t n_rows, uint32_t win_lo, uint32_t win_n, bool rows) {
@@ -541,6 +814,29 @@ size_t explain_scratch_bytes(int32_t plugin_set, uint32_t extent, uint32_t n_pod
 }
 
 ms_explain_summary *explain_summaries(void *scratch) { return ex_layout(scratch, 0, 1, 1).sums; }
+
+size_t explain_shard_scratch_bytes(const ExplainArgs &a) {
+    return ex_layout(nullptr, a.plugin_set, shard_extent(a), a.n_pods, a.n_shards).bytes;
+}
+
+ExplainExchange explain_exchange(const ExplainArgs &a) {
+    const ExScratch x = ex_layout(a.scratch, a.plugin_set, shard_extent(a), a.n_pods, a.n_shards);
+    return ExplainExchange{x.shard_all, sizeof(ExShard), x.best_all};
+}
+
+hipError_t launch_explain_shard(const ExplainArgs &a, ExplainShardStage stage, uint32_t p0, uint32_t nb, hipStream_t s) {
+    if (a.n_pods == 0 || a.n_pods > MS_EXPLAIN_MAX_PODS || !a.scratch || a.n_shards == 0 || a.shard >= a.n_shards ||
+        p0 + nb > a.n_pods)
+        return hipErrorInvalidValue;
+    switch (a.plugin_set) {
+        case MS_PLUGINS_NU_NN: return launch_shard_set<MS_PLUGINS_NU_NN>(a, stage, p0, nb, s);
+        case MS_PLUGINS_NU_NRF_NN_LA: return launch_shard_set<MS_PLUGINS_NU_NRF_NN_LA>(a, stage, p0, nb, s);
+        case MS_PLUGINS_NU_NN_NA: return launch_shard_set<MS_PLUGINS_NU_NN_NA>(a, stage, p0, nb, s);
+        case MS_PLUGINS_NU_TT_NN: return launch_shard_set<MS_PLUGINS_NU_TT_NN>(a, stage, p0, nb, s);
+        case MS_PLUGINS_NU_NN_NAM: return launch_shard_set<MS_PLUGINS_NU_NN_NAM>(a, stage, p0, nb, s);
+    }
+    return hipErrorInvalidValue;
+}
 
 hipError_t launch_explain(const ExplainArgs &a, hipStream_t s) {
     if (a.n_pods == 0) return hipSuccess;

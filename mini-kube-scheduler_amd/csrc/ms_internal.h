@@ -481,6 +481,9 @@ struct ExplainArgs {
     ms_explain_row *rows = nullptr;  // n_pods x win_n, or null
     bool summaries = false;          // whole-table summaries (with best_key) into explain_summaries(scratch)
     void *scratch = nullptr;         // explain_scratch_bytes
+    // node shards (launch_explain_shard only): the communicator's world and this
+    // context's rank; n_pods is then the whole call's, rows a chunk's staging
+    uint32_t n_shards = 0, shard = 0;
 };
 // Local rows the call's tiles cover and the scratch they need.
 uint32_t explain_extent(uint32_t n_rows, uint32_t win_lo, uint32_t win_n, bool rows);
@@ -489,6 +492,33 @@ size_t explain_scratch_bytes(int32_t plugin_set, uint32_t extent, uint32_t n_pod
 ms_explain_summary *explain_summaries(void *scratch);
 // Tile summaries, the per-pod scan over the tiles, then the rows (and the best keys).
 hipError_t launch_explain(const ExplainArgs &a, hipStream_t s);
+// Explain on node shards (ms_explain_sharded_device): a shard is one
+// more tile. The stages of one call, in this order on one stream, between them
+// the two all-gathers of explain_exchange's buffers (in place: this rank's block
+// is block `shard`); none waits on a value another rank wrote.
+enum ExplainShardStage {
+    kExShardRecords,  // the tiles' records of all n_pods pods, then this shard's record per pod
+    kExShardScan,     // after the records' all-gather: the scan started from the G shards' records
+    kExShardRows,     // pods [p0, p0 + nb): every tile's best key, the window's rows into a.rows (nb x win_n)
+    kExShardBest,     // this shard's best key per pod, from every chunk's tiles
+    kExShardMax,      // after the keys' all-gather: the summaries' best_key = the maximum over the shards
+};
+// The window counts whether or not rows are asked for (win_n = 0: no rows).
+size_t explain_shard_scratch_bytes(const ExplainArgs &a);
+struct ExplainExchange {
+    void *records;        // n_shards x n_pods opaque records of record_bytes, shard-major
+    size_t record_bytes;
+    unsigned long long *best;  // n_shards x n_pods keys, shard-major
+};
+ExplainExchange explain_exchange(const ExplainArgs &a);
+hipError_t launch_explain_shard(const ExplainArgs &a, ExplainShardStage stage, uint32_t p0, uint32_t nb,
+                                hipStream_t s);
+
+// ---- node-shard exchange (ms_comm.cpp) -------------------------------------
+// One all-gather over the context's communicator on s: `bytes` bytes from send
+// into block `rank` of every rank's recv (send may be that block of recv). The
+// callers outside ms_comm.cpp name no RCCL entry point. MS_OK or MS_E_RCCL.
+int comm_all_gather(ms_ctx *c, const void *send, void *recv, size_t bytes, hipStream_t s);
 
 // ---- launchers (ms_kernels.hip), continued: decodes, binds, read-back ------
 // One launch decoding several batches' pod slices, each with a device-side present flag.

@@ -312,6 +312,8 @@ SIGNATURES = {
     "ms_sharded_slice": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "ms_sharded_submit": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp]),
     "ms_sharded_drain": (ctypes.c_int, [_vp, _vp]),
+    "ms_explain_sharded_device": (ctypes.c_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "ms_explain_sharded": (ctypes.c_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp]),
 }
 
 DECODE_MAX_JOBS = 8  # MS_DECODE_MAX_JOBS
@@ -670,6 +672,32 @@ class Engine:
 
     def sharded_drain(self, stream=0):
         self._check("ms_sharded_drain", self.lib.ms_sharded_drain(self.h, stream or None))
+
+    def explain_sharded(self, pods: np.ndarray, first: Optional[int] = None, n_nodes: Optional[int] = None,
+                        rows: bool = True, summaries: bool = True):
+        """ms_explain_sharded on a context joined to a communicator (comm_init):
+        Engine.explain over the cluster's LIST. Collective: every rank calls with
+        the same pods; the window (default: this context's own node range) and
+        the outputs are the rank's own. Returns (rows[n_pods, n_nodes] of this
+        rank's window, summaries[n_pods] of the whole cluster, the same on every
+        rank); rows=False / summaries=False passes NULL and returns None in its
+        place, and with both False the rank only takes part in the exchange."""
+        p = np.ascontiguousarray(pods, dtype=POD_REC)
+        first = self.node_base if first is None else int(first)
+        n_nodes = self.node_base + self.max_nodes - first if n_nodes is None else int(n_nodes)
+        r = np.zeros((len(p), n_nodes), dtype=EXPLAIN_ROW) if rows else None
+        s = np.zeros(len(p), dtype=EXPLAIN_SUMMARY) if summaries else None
+        self._check("ms_explain_sharded", self.lib.ms_explain_sharded(self.h, len(p), _ptr(p), first,
+                                                                      n_nodes if rows else 0, _ptr(r), _ptr(s)))
+        return r, s
+
+    def explain_sharded_device(self, n_pods, pods_dev, first, n_nodes, rows_dev, summaries_dev, stream=0):
+        """ms_explain_sharded_device on device-resident pods (collective): rows_dev
+        (n_pods x n_nodes EXPLAIN_ROW of this rank's window) or 0, summaries_dev
+        (n_pods EXPLAIN_SUMMARY) or 0; both 0: the exchange alone."""
+        self._check("ms_explain_sharded_device",
+                    self.lib.ms_explain_sharded_device(self.h, n_pods, pods_dev, first, n_nodes, rows_dev or None,
+                                                       summaries_dev or None, stream or None))
 
     def schedule_sequential_device(self, n_pods, pods_dev, results_dev, stream=0):
         self._check(
