@@ -250,7 +250,24 @@ int ms_last_call_profile(const ms_ctx *ctx, ms_call_profile *out);
 /* ---- node deltas (informer Add/Update/Delete, eventhandler.go:60-76) ------
  * Enqueued under a mutex (safe from informer goroutines while another thread
  * schedules); drained stream-ordered at the start of the next schedule call
- * or by ms_nodes_flush. Later deltas to one ordinal win. */
+ * or by ms_nodes_flush. Later deltas to one ordinal win: within one drain an
+ * upsert after a delete re-adds the row, a delete after an upsert removes it.
+ * A call with an ordinal outside the context's range returns MS_E_CAPACITY and
+ * queues none of its deltas. ms_info.present_nodes counts queued deltas at once;
+ * ms_info.pending_deltas is the queue's length, repeats included.
+ *
+ * Who drains. These apply every queued delta before their own work:
+ * ms_nodes_flush, ms_nodes_read, ms_commit_bind, ms_uncommit_bind,
+ * ms_schedule_batch(_compact), ms_sweep_device, ms_select_batch_device,
+ * ms_schedule_sequential_device, ms_seq_candidates_device,
+ * ms_tt_summaries_device, ms_tt_census_device, ms_nam_segment_device,
+ * ms_explain(_device). These never do, and work on the table of the last drain:
+ * ms_decode_device(_jobs), ms_apply_binds_device, ms_seq_validate_device,
+ * ms_tt_decode_device, ms_tt_pick_device, ms_tt_final_device,
+ * ms_nam_keys_device, ms_nam_flags_device, ms_get_info, ms_seq_counters,
+ * ms_last_call_profile. So a cycle of several calls (the node-sharded
+ * protocols below) sees one table from its step 1 to its last step; a delta
+ * queued meanwhile is seen by the next cycle's step 1. */
 int ms_nodes_upsert(ms_ctx *ctx, uint32_t n, const uint32_t *ordinals, const ms_node_rec *recs);
 int ms_nodes_delete(ms_ctx *ctx, uint32_t n, const uint32_t *ordinals);
 int ms_nodes_flush(ms_ctx *ctx);
@@ -273,7 +290,9 @@ int ms_schedule_batch_compact(ms_ctx *ctx, uint32_t n_pods, const ms_pod_compact
                               ms_result_compact *out);
 
 /* Assume / forget for the live scheduler (upstream cache.AssumePod/ForgetPod):
- * add / remove one pod's requests on a node. */
+ * add / remove one pod's requests on a node. Queued deltas are drained first;
+ * a node that is then not present (deleted, or never added) is refused with
+ * MS_E_INVAL and the table is left untouched. */
 int ms_commit_bind(ms_ctx *ctx, uint32_t ordinal, const ms_pod_rec *pod);
 int ms_uncommit_bind(ms_ctx *ctx, uint32_t ordinal, const ms_pod_rec *pod);
 
@@ -397,7 +416,10 @@ int ms_tt_decode_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev
  *   3. ms_tt_pick_device: this shard's keys (keys_dev, n_pods x u64) under the
  *      plan every shard's census implies;
  *   4. the element-wise uint64 MAX of the shards' keys;
- *   5. ms_tt_final_device (any shard): each pod's result (no bind commit). */
+ *   5. ms_tt_final_device (any shard): each pod's result (no bind commit).
+ * No deltas are drained between 1 and 5: steps 3 and 5 read the table step 1
+ * read, the one every shard's census describes. A delta queued meanwhile is
+ * seen by the next cycle's step 1. */
 #define MS_TT_CENSUS_BYTES 32u
 int ms_tt_census_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev, void *census_dev, void *stream);
 int ms_tt_pick_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev, uint32_t n_shards,
@@ -456,7 +478,10 @@ int ms_nam_term_sets_ext(ms_ctx *ctx, uint32_t n_sets, const ms_nam_term_set_ext
  *      every later node of the cluster, the first non-zero node of the cluster
  *      at 100. The element-wise uint64 MAX over the shards is selectHost over
  *      the cluster; ms_decode_device turns it into results (flags NULL, or
- *      ms_nam_flags_device's once a required set is registered, below). */
+ *      ms_nam_flags_device's once a required set is registered, below).
+ * No deltas are drained between 1 and the decode: step 3 reads the table step 1
+ * read, the one every shard's record describes. A delta queued meanwhile is
+ * seen by the next cycle's step 1. */
 #define MS_NAM_SEG_BYTES 104u
 int ms_nam_segment_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev, void *seg_dev, void *stream);
 int ms_nam_keys_device(ms_ctx *ctx, uint32_t n_pods, const ms_pod_rec *pods_dev, uint32_t n_shards,

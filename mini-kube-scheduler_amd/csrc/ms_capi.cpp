@@ -382,6 +382,13 @@ static int bind_common(ms_ctx *c, uint32_t ordinal, const ms_pod_rec *pod, int s
     MS_HIP(c, hipSetDevice(c->cfg.device));
     int rc = flush_locked(c);
     if (rc) return rc;
+    {
+        // present[] counts queued deltas; a bind drains first, so it is the row's
+        // state on the device unless a delta arrived since (then the newest word)
+        std::lock_guard<std::mutex> d(c->delta_mu);
+        if (!c->present[ordinal - c->cfg.node_base])
+            return fail(c, MS_E_INVAL, "bind: node " + std::to_string(ordinal) + " is not present");
+    }
     rc = fence_ctx(c);  // (the bind writes the table: after in-flight sharded sweeps)
     if (rc < 0) return rc;
     // the context stream already waits for earlier caller-stream work (OrderedCall::done)

@@ -429,7 +429,8 @@ int ms_tt_pick_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, ui
     if (n_pods == 0) return c->cfg.plugin_set == MS_PLUGINS_NU_TT_NN ? MS_OK : MS_E_INVAL;
     int rc = tt_only(c, "ms_tt_pick_device");
     if (rc) return rc;
-    OrderedCall call(c, stream);
+    // mid-cycle: no deltas drained, the table stays the one step 1 saw (as ms_seq_validate_device)
+    OrderedCall call(c, stream, false);
     if (call.rc()) return call.rc();
     const hipStream_t s = call.stream();
     rc = tt2_shard_begin(c, n_pods, s);
@@ -455,7 +456,8 @@ int ms_tt_final_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, u
     if (n_pods == 0) return c->cfg.plugin_set == MS_PLUGINS_NU_TT_NN ? MS_OK : MS_E_INVAL;
     int rc = tt_only(c, "ms_tt_final_device");
     if (rc) return rc;
-    OrderedCall call(c, stream);
+    // mid-cycle: no deltas drained, the table stays the one step 1 saw (as ms_seq_validate_device)
+    OrderedCall call(c, stream, false);
     if (call.rc()) return call.rc();
     const hipStream_t s = call.stream();
     rc = tt2_shard_begin(c, n_pods, s, false);  // (the final pass reads no planes)
@@ -511,7 +513,8 @@ int ms_nam_keys_device(ms_ctx *c, uint32_t n_pods, const ms_pod_rec *pods_dev, u
     if (n_shards == 0 || shard_index >= n_shards)
         return fail(c, MS_E_INVAL, "ms_nam_keys_device: shard_index must be below n_shards");
     if (n_pods == 0) return MS_OK;
-    OrderedCall call(c, stream);
+    // mid-cycle: no deltas drained, the table stays the one step 1 saw (as ms_seq_validate_device)
+    OrderedCall call(c, stream, false);
     if (call.rc()) return call.rc();
     const hipStream_t s = call.stream();
     const NamPlan plan = nam_plan_for(c, n_pods);
